@@ -132,11 +132,12 @@ def sharded_sddmm(dist, rank, world, ro, counts_offsets, compute, local_out, roo
 
 
 def run_sharded(eng, torch, dist, dev, rank, world, make_pattern, K, alpha, delta, mode, steps, warmup,
-                scaling="weak", strong_rows=None):
+                scaling="weak", strong_rows=None, keep_output=False):
     """bench.py's N > 1 path.  weak scaling: the job is `world` row-stacked patterns
     (rank r generates and owns copy r); strong: one pattern cut into `world` ranges - with `strong_rows` =
     (row costs of the whole pattern, make_rows(first_row, rows)) every rank builds ONLY its own rows, the
-    boundaries come from the cost partition."""
+    boundaries come from the cost partition.  keep_output: rank 0's result also carries "output", a copy of the
+    P the last timed step gathered (device tensor, total nnz entries)."""
     import time
 
     if scaling == "weak":
@@ -208,6 +209,8 @@ def run_sharded(eng, torch, dist, dev, rank, world, make_pattern, K, alpha, delt
     torch.cuda.synchronize()
     dist.barrier()
     dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+    # the buffers are written again below: the last timed step's P is copied first
+    last_output = root_outs[(runner.index - 1) & 1].clone() if keep_output and rank == 0 else None
     dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     ms = float(dt.item()) / steps * 1e3
 
@@ -231,7 +234,7 @@ def run_sharded(eng, torch, dist, dev, rank, world, make_pattern, K, alpha, delt
     dist.barrier()
     gt = torch.tensor([(time.perf_counter() - g0) / reps * 1e3], dtype=torch.float64, device=dev)
     dist.all_reduce(gt, op=dist.ReduceOp.MAX)
-    return {
+    result = {
         "metric": "SDDMM GFLOP/s", "value": round(2.0 * total_nnz * K / (ms * 1e6), 2), "unit": "GFLOP/s",
         "ms_per_step": round(ms, 5), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
         "data": "synthetic",
@@ -250,3 +253,6 @@ def run_sharded(eng, torch, dist, dev, rank, world, make_pattern, K, alpha, delt
                   "union_columns": pipe.dense_choice(K)["union_columns"], "sparse_nnz": pipe.plan_stats()["num_sparse_entries"],
                   "sparse_lowp": bool(pipe.sparse_choice(K, mode)["low_precision"])},
     }
+    if last_output is not None:
+        result["output"] = last_output
+    return result
