@@ -1,0 +1,286 @@
+// The SDDMM backward (include/bsmr_hip.h "SDDMM backward"): a per-pattern handle holding S's CSR, its transpose and the
+// chunked work lists of both directions, and the two calls that run csrc/spmm_kernels.hpp on them.
+//
+// Host side (no device call before everything is validated, so that a CPU test can check the rejections):
+//   * the transpose is a stable counting sort by column: within a column, entries in ascending row = ascending CSR index;
+//   * every destination list (a row for dA, a column for dB) longer than BSMR_BACKWARD_CHUNK is cut into chunks of that
+//     length; the chunk table (which destinations are split, their workspace rows) depends on the pattern alone;
+//   * the rows are scheduled in row_order (then every row it omits, in natural order), the columns in natural order -
+//     rows with similar column sets run side by side and reuse the same rows of B in L2.
+// Included at the end of bsmr_capi.hip.
+#pragma once
+
+#include "spmm_kernels.hpp"
+
+struct bsmr_backward {
+    int device = 0;
+    uint32_t M = 0, N = 0, nnz = 0;
+    uint32_t* colIndices = nullptr;   // [nnz]  s(t) of the row direction
+    uint32_t* cscRows = nullptr;      // [nnz]  s(t) of the column direction
+    uint32_t* cscToCsr = nullptr;     // [nnz]  e(t) of the column direction
+    bsmr::BwItem* items[2] = {nullptr, nullptr};
+    bsmr::BwSplit* splits[2] = {nullptr, nullptr};
+    uint32_t numItems[2] = {0, 0}, numSplits[2] = {0, 0}, numSlots[2] = {0, 0}, maxLen[2] = {0, 0};
+    bool permuteV = true;             // dB reads dP permuted into CSC order by a pass of its own (measured faster on 3 of
+                                      // the 4 lab shapes); BSMR_BACKWARD_PERMUTE=0: through csc_to_csr in place
+    uint64_t indexBytes = 0;
+    float* work = nullptr;            // chunk partials (+ permuted dP), grown on demand
+    uint64_t workFloats = 0;
+
+    ~bsmr_backward() {
+        for (void* p : {(void*)colIndices, (void*)cscRows, (void*)cscToCsr, (void*)items[0], (void*)items[1],
+                        (void*)splits[0], (void*)splits[1], (void*)work})
+            if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+// CSR checks shared by bsmr_csr_transpose and bsmr_backward_create
+int checkCsr(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* ro, const uint32_t* ci) {
+    if (!ro || (nnz && !ci)) return BSMR_ERR_INVALID_ARG;
+    if (ro[0] != 0 || ro[M] != nnz) return BSMR_ERR_INVALID_ARG;
+    for (uint32_t r = 0; r < M; ++r)
+        if (ro[r + 1] < ro[r]) return BSMR_ERR_INVALID_ARG;
+    for (uint32_t t = 0; t < nnz; ++t)
+        if (ci[t] >= N) return BSMR_ERR_INVALID_ARG;
+    return BSMR_OK;
+}
+
+void csrTranspose(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* ro, const uint32_t* ci, uint32_t* co,
+                  uint32_t* cscRows, uint32_t* cscToCsr) {
+    std::fill(co, co + N + 1, 0u);
+    for (uint32_t t = 0; t < nnz; ++t) ++co[ci[t] + 1];
+    for (uint32_t c = 0; c < N; ++c) co[c + 1] += co[c];
+    std::vector<uint32_t> next(co, co + N);
+    for (uint32_t r = 0; r < M; ++r)
+        for (uint32_t t = ro[r]; t < ro[r + 1]; ++t) {
+            const uint32_t p = next[ci[t]]++;
+            cscRows[p] = r;
+            cscToCsr[p] = t;
+        }
+}
+
+// Work lists of one direction: offsets[numDest + 1] are the list bounds, `order` the schedule of the destinations.
+void buildItems(const uint32_t* offsets, uint32_t numDest, const std::vector<uint32_t>& order,
+                std::vector<bsmr::BwItem>& items, std::vector<bsmr::BwSplit>& splits, uint32_t& numSlots, uint32_t& maxLen) {
+    constexpr uint32_t C = BSMR_BACKWARD_CHUNK;
+    std::vector<uint32_t> firstSlot(numDest, bsmr::kBwDirect);
+    numSlots = maxLen = 0;
+    for (uint32_t d = 0; d < numDest; ++d) {   // the chunk table: natural destination order, whatever the schedule
+        const uint32_t len = offsets[d + 1] - offsets[d];
+        maxLen = std::max(maxLen, len);
+        if (len > C) {
+            const uint32_t chunks = (len + C - 1) / C;
+            firstSlot[d] = numSlots;
+            splits.push_back({d, numSlots, chunks, 0});
+            numSlots += chunks;
+        }
+    }
+    items.reserve(numDest + numSlots);
+    for (uint32_t d : order) {
+        const uint32_t b = offsets[d], e = offsets[d + 1];
+        if (firstSlot[d] == bsmr::kBwDirect) {
+            items.push_back({d, b, e, bsmr::kBwDirect});
+            continue;
+        }
+        for (uint32_t k = 0, t = b; t < e; ++k, t += C) items.push_back({d, t, std::min(e, t + C), firstSlot[d] + k});
+    }
+}
+
+uint64_t workFloatsFor(const bsmr_backward* bw, uint32_t K, uint32_t nb, bool withPermute) {
+    const uint64_t slots = std::max(bw->numSlots[0], bw->numSlots[1]);
+    return (slots * K + (withPermute ? bw->nnz : 0u)) * nb;
+}
+
+int growWork(bsmr_backward* bw, uint64_t floats) {
+    if (floats <= bw->workFloats) return BSMR_OK;
+    if (bw->work) BSMR_HIP(hipFree(bw->work));
+    bw->work = nullptr;
+    bw->workFloats = 0;
+    if (!hipOk(hipMalloc(reinterpret_cast<void**>(&bw->work), floats * sizeof(float)), "hipMalloc(backward workspace)"))
+        return BSMR_ERR_OOM;
+    bw->workFloats = floats;
+    return BSMR_OK;
+}
+
+int checkBackwardCall(const bsmr_backward* bw, uint32_t K, uint32_t nb) {
+    if (!bw) return BSMR_ERR_INVALID_ARG;
+    if (K == 0 || (K & 31u)) return BSMR_ERR_UNSUPPORTED_K;
+    if (nb > 65535u) return BSMR_ERR_INVALID_ARG;
+    return BSMR_OK;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.
+int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const float* X, float* Y, uint32_t nb, hipStream_t s) {
+    const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
+    const uint64_t nnz = bw->nnz;
+    const uint64_t xB = (uint64_t)rowsX * K, yB = (uint64_t)rowsY * K, pB = (uint64_t)bw->numSlots[dir] * K;
+    float* partial = bw->work;
+    const uint32_t* map = dir ? bw->cscToCsr : nullptr;
+    if (dir && bw->permuteV && nnz) {   // dP in CSC order, behind the partials of the workspace
+        float* vT = bw->work + pB * nb;
+        hipLaunchKernelGGL(bsmr::spmmPermute, dim3((bw->nnz + 255u) / 256u, nb), dim3(256), 0, s, bw->cscToCsr, bw->nnz, v, vT);
+        BSMR_HIP(hipGetLastError());
+        v = vT;
+        map = nullptr;
+    }
+    const uint32_t* src = dir ? bw->cscRows : bw->colIndices;
+    const uint32_t W = K % 256u == 0 ? 256u : K % 128u == 0 ? 128u : K % 64u == 0 ? 64u : 32u;
+    const uint32_t slices = K / W;
+    const uint64_t units = (uint64_t)bw->numItems[dir] * slices;
+    const uint64_t unitsPerBlock = 4u * (W >= 128u ? 1u : 64u / (W / 4u));
+    const dim3 grid((uint32_t)((units + unitsPerBlock - 1) / unitsPerBlock), nb);
+    if (units) {
+#define BSMR_SPMM_LAUNCH(WW, MAP)                                                                                            \
+    hipLaunchKernelGGL((bsmr::spmmGather<WW, MAP>), grid, dim3(256), 0, s, bw->items[dir], bw->numItems[dir], slices, src, \
+                       map, v, X, Y, partial, K, nnz, xB, yB, pB)
+        const bool m = map != nullptr;
+        switch (W) {
+        case 256: if (m) BSMR_SPMM_LAUNCH(256, true); else BSMR_SPMM_LAUNCH(256, false); break;
+        case 128: if (m) BSMR_SPMM_LAUNCH(128, true); else BSMR_SPMM_LAUNCH(128, false); break;
+        case 64: if (m) BSMR_SPMM_LAUNCH(64, true); else BSMR_SPMM_LAUNCH(64, false); break;
+        default: if (m) BSMR_SPMM_LAUNCH(32, true); else BSMR_SPMM_LAUNCH(32, false); break;
+        }
+#undef BSMR_SPMM_LAUNCH
+        BSMR_HIP(hipGetLastError());
+    }
+    if (bw->numSplits[dir]) {
+        const uint64_t threads = (uint64_t)bw->numSplits[dir] * (K / 4u);
+        hipLaunchKernelGGL(bsmr::spmmReduce, dim3((uint32_t)((threads + 255u) / 256u), nb), dim3(256), 0, s, bw->splits[dir],
+                           bw->numSplits[dir], partial, Y, K, yB, pB);
+        BSMR_HIP(hipGetLastError());
+    }
+    return BSMR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bsmr_csr_transpose(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* row_offsets, const uint32_t* col_indices,
+                       uint32_t* col_offsets, uint32_t* csc_rows, uint32_t* csc_to_csr) {
+    if (!col_offsets || (nnz && (!csc_rows || !csc_to_csr))) return BSMR_ERR_INVALID_ARG;
+    if (int st = checkCsr(M, N, nnz, row_offsets, col_indices)) return st;
+    csrTranspose(M, N, nnz, row_offsets, col_indices, col_offsets, csc_rows, csc_to_csr);
+    return BSMR_OK;
+}
+
+int bsmr_backward_create(bsmr_backward** out, int device, uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* row_offsets,
+                         const uint32_t* col_indices, const uint32_t* row_order, uint32_t num_ordered_rows) {
+    if (!out) return BSMR_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (num_ordered_rows && !row_order) return BSMR_ERR_INVALID_ARG;
+    if (int st = checkCsr(M, N, nnz, row_offsets, col_indices)) return st;
+    std::vector<uint32_t> order;
+    try {
+        std::vector<uint8_t> seen(M, 0);
+        order.reserve(M);
+        for (uint32_t i = 0; i < num_ordered_rows; ++i) {
+            const uint32_t r = row_order[i];
+            if (r >= M || seen[r]) return BSMR_ERR_INVALID_ARG;
+            seen[r] = 1;
+            order.push_back(r);
+        }
+        for (uint32_t r = 0; r < M; ++r)
+            if (!seen[r]) order.push_back(r);
+    } catch (const std::bad_alloc&) {
+        return BSMR_ERR_OOM;
+    }
+    if (int st = useDevice(device)) return st;
+    std::unique_ptr<bsmr_backward> bw;
+    try {
+        bw.reset(new bsmr_backward());
+        bw->device = device;
+        bw->M = M;
+        bw->N = N;
+        bw->nnz = nnz;
+        const char* perm = std::getenv("BSMR_BACKWARD_PERMUTE");
+        bw->permuteV = !perm || std::atoi(perm) != 0;
+        std::vector<uint32_t> co(N + 1u), cscRows(nnz), cscToCsr(nnz), ci(col_indices, col_indices + nnz);
+        csrTranspose(M, N, nnz, row_offsets, col_indices, co.data(), cscRows.data(), cscToCsr.data());
+        std::vector<uint32_t> cols(N);
+        for (uint32_t c = 0; c < N; ++c) cols[c] = c;
+        std::vector<bsmr::BwItem> items[2];
+        std::vector<bsmr::BwSplit> splits[2];
+        buildItems(row_offsets, M, order, items[0], splits[0], bw->numSlots[0], bw->maxLen[0]);
+        buildItems(co.data(), N, cols, items[1], splits[1], bw->numSlots[1], bw->maxLen[1]);
+        if (items[0].size() > 0xFFFFFFFFull || items[1].size() > 0xFFFFFFFFull) return BSMR_ERR_INVALID_ARG;
+        uint64_t& bytes = bw->indexBytes;
+        if (int st = upload(bw->colIndices, ci, bytes)) return st;
+        if (int st = upload(bw->cscRows, cscRows, bytes)) return st;
+        if (int st = upload(bw->cscToCsr, cscToCsr, bytes)) return st;
+        for (int d = 0; d < 2; ++d) {
+            if (int st = upload(bw->items[d], items[d], bytes)) return st;
+            if (int st = upload(bw->splits[d], splits[d], bytes)) return st;
+            bw->numItems[d] = (uint32_t)items[d].size();
+            bw->numSplits[d] = (uint32_t)splits[d].size();
+        }
+    } catch (const std::bad_alloc&) {
+        return BSMR_ERR_OOM;
+    }
+    *out = bw.release();
+    return BSMR_OK;
+}
+
+int bsmr_backward_destroy(bsmr_backward* bw) {
+    if (!bw) return BSMR_OK;
+    (void)hipSetDevice(bw->device);
+    delete bw;
+    return BSMR_OK;
+}
+
+int bsmr_backward_reserve(bsmr_backward* bw, uint32_t K, uint32_t num_batches) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    BSMR_HIP(hipSetDevice(bw->device));
+    return growWork(bw, workFloatsFor(bw, K, std::max(num_batches, 1u), bw->permuteV));
+}
+
+int bsmr_backward_get_stats(const bsmr_backward* bw, bsmr_backward_stats* out, size_t out_size) {
+    if (!bw || !out) return BSMR_ERR_INVALID_ARG;
+    bsmr_backward_stats full{};
+    full.chunk = BSMR_BACKWARD_CHUNK;
+    full.split_rows = bw->numSplits[0];
+    full.split_cols = bw->numSplits[1];
+    full.max_row_length = bw->maxLen[0];
+    full.max_col_length = bw->maxLen[1];
+    full.row_items = bw->numItems[0];
+    full.col_items = bw->numItems[1];
+    full.device_index_bytes = bw->indexBytes;
+    full.workspace_bytes = bw->workFloats * sizeof(float);
+    full.permute_values = bw->permuteV ? 1u : 0u;
+    memcpy(out, &full, std::min(out_size, sizeof(full)));   // (the struct only grows at its end)
+    return BSMR_OK;
+}
+
+int bsmr_spmm(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, const float* X_dev, float* Y_dev,
+              uint32_t num_batches, void* stream) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
+    if (!v_dev || !X_dev || !Y_dev || !aligned16(X_dev) || !aligned16(Y_dev)) return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0) return BSMR_OK;
+    BSMR_HIP(hipSetDevice(bw->device));
+    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
+    return runSpmm(bw, K, transpose, v_dev, X_dev, Y_dev, num_batches, static_cast<hipStream_t>(stream));
+}
+
+int bsmr_sddmm_backward(bsmr_backward* bw, uint32_t K, const float* dP_dev, const float* A_dev, const float* B_dev,
+                        float* dA_dev, float* dB_dev, uint32_t num_batches, void* stream) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    if (!dP_dev || (dA_dev && (!B_dev || !aligned16(B_dev) || !aligned16(dA_dev))) ||
+        (dB_dev && (!A_dev || !aligned16(A_dev) || !aligned16(dB_dev))))
+        return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0 || (!dA_dev && !dB_dev)) return BSMR_OK;
+    BSMR_HIP(hipSetDevice(bw->device));
+    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && dB_dev))) return st;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dA_dev)
+        if (int st = runSpmm(bw, K, 0, dP_dev, B_dev, dA_dev, num_batches, s)) return st;
+    if (dB_dev)
+        if (int st = runSpmm(bw, K, 1, dP_dev, A_dev, dB_dev, num_batches, s)) return st;
+    return BSMR_OK;
+}
+
+}  // extern "C"

@@ -3686,3 +3686,4 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
 
 #include "sharded_capi.hpp"
 #include "colreorder_capi.hpp"
+#include "backward_capi.hpp"

@@ -119,6 +119,13 @@ class ShardedTiming(C.Structure):
                 ("gather_ms", C.c_float)]
 
 
+class BackwardStats(C.Structure):
+    _fields_ = [("chunk", C.c_uint32), ("split_rows", C.c_uint32), ("split_cols", C.c_uint32),
+                ("max_row_length", C.c_uint32), ("max_col_length", C.c_uint32), ("row_items", C.c_uint32),
+                ("col_items", C.c_uint32), ("permute_values", C.c_uint32), ("device_index_bytes", C.c_uint64),
+                ("workspace_bytes", C.c_uint64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("convert_ms", C.c_float), ("dense_ms", C.c_float),
                 ("sparse_ms", C.c_float)]
@@ -191,6 +198,16 @@ HIP_SYMBOLS = {
     "bsmr_sharded_num_entries": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bsmr_sharded_sddmm_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                           C.POINTER(ShardedTiming)]),
+    "bsmr_backward_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_uint32]),
+    "bsmr_backward_destroy": (C.c_int, [C.c_void_p]),
+    "bsmr_backward_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "bsmr_backward_get_stats": (C.c_int, [C.c_void_p, C.POINTER(BackwardStats), C.c_size_t]),
+    "bsmr_csr_transpose": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "bsmr_spmm": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bsmr_sddmm_backward": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_uint32, C.c_void_p]),
 }
 
 HOST_SYMBOLS = {
@@ -648,3 +665,59 @@ def plan_from_arrays(M, N, nnz, arrays: dict, device=0, options: PlanOptions = N
 
 def plan_destroy(plan):
     hip().bsmr_plan_destroy(plan)
+
+
+# --- SDDMM backward (bsmr_backward_*, bsmr_spmm, bsmr_sddmm_backward; pointers are integers) ---
+def csr_transpose(rows, cols, row_offsets, col_indices):
+    """bsmr_csr_transpose (host only): (col_offsets, csc_rows, csc_to_csr)"""
+    ro = np.ascontiguousarray(row_offsets, dtype=np.uint32)
+    ci = np.ascontiguousarray(col_indices, dtype=np.uint32)
+    co = np.zeros(cols + 1, dtype=np.uint32)
+    rws = np.zeros(max(ci.size, 1), dtype=np.uint32)
+    e = np.zeros(max(ci.size, 1), dtype=np.uint32)
+    _check(hip().bsmr_csr_transpose(rows, cols, ci.size, _ptr(ro), _ptr(ci), _ptr(co), _ptr(rws), _ptr(e)),
+           "bsmr_csr_transpose")
+    return co, rws[:ci.size], e[:ci.size]
+
+
+def backward_create_status(rows, cols, row_offsets, col_indices, row_order=None, device=0):
+    """bsmr_backward_create: (status, handle); row_order None = natural order"""
+    ro = np.ascontiguousarray(row_offsets, dtype=np.uint32)
+    ci = np.ascontiguousarray(col_indices, dtype=np.uint32)
+    order = None if row_order is None else np.ascontiguousarray(row_order, dtype=np.uint32)
+    out = C.c_void_p()
+    st = hip().bsmr_backward_create(C.byref(out), device, rows, cols, ci.size, _ptr(ro), _ptr(ci) if ci.size else None,
+                                    _ptr(order) if order is not None and order.size else None,
+                                    0 if order is None else order.size)
+    return st, out
+
+
+def backward_create(rows, cols, row_offsets, col_indices, row_order=None, device=0):
+    st, h = backward_create_status(rows, cols, row_offsets, col_indices, row_order, device)
+    _check(st, "bsmr_backward_create")
+    return h
+
+
+def backward_destroy(bw):
+    hip().bsmr_backward_destroy(bw)
+
+
+def backward_reserve(bw, K: int, num_batches: int = 1):
+    _check(hip().bsmr_backward_reserve(bw, K, num_batches), "bsmr_backward_reserve")
+
+
+def backward_stats(bw) -> dict:
+    s = BackwardStats()
+    _check(hip().bsmr_backward_get_stats(bw, C.byref(s), C.sizeof(s)), "bsmr_backward_get_stats")
+    return {k: getattr(s, k) for k, _ in BackwardStats._fields_}
+
+
+def spmm(bw, K: int, transpose: bool, v_ptr: int, X_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0):
+    """Y = S_v X (transpose False) or S_v^T X (True)"""
+    _check(hip().bsmr_spmm(bw, K, int(bool(transpose)), v_ptr, X_ptr, Y_ptr, num_batches, stream), "bsmr_spmm")
+
+
+def sddmm_backward(bw, K: int, dP_ptr: int, A_ptr: int, B_ptr: int, dA_ptr, dB_ptr, num_batches: int = 1, stream: int = 0):
+    """dA = S_dP B, dB = S_dP^T A; dA_ptr / dB_ptr None (or 0) skips that product"""
+    _check(hip().bsmr_sddmm_backward(bw, K, dP_ptr, A_ptr, B_ptr, dA_ptr or None, dB_ptr or None, num_batches, stream),
+           "bsmr_sddmm_backward")

@@ -1,0 +1,174 @@
+"""torch entry point of the engine: one sparsity pattern S, its SDDMM and SpMM as differentiable operators.
+
+    op = SparseOperator(csr)                 # pipeline (clustered rows), SDDMM plan, backward handle
+    P = op.sddmm(A, B)                       # P[t] = A[row(t)] . B[col(t)]           (nnz,) or (b, nnz)
+    Y = op.spmm(values, X)                   # Y = S_values X     (transpose=True: S_values^T X)
+
+Both are torch.autograd.Functions whose backward runs on the engine (bsmr_sddmm_backward, bsmr_spmm, bsmr_sddmm):
+    sddmm:  dA = S_dP B,  dB = S_dP^T A      (exact fp32 products of the given operands in every mode: the forward's
+                                              operand rounding is treated as straight-through)
+    spmm:   d values = sddmm(dY, X)  (transposed: sddmm(X, dY)),  dX = spmm(values, dY, not transpose)
+so SDDMM -> softmax in torch -> SpMM, the usual sparse-attention layer, trains on the engine end to end.
+
+Every call runs on torch.cuda.current_stream(device).  Operands are fp32, contiguous, on the operator's device, with
+K a positive multiple of 32; anything else raises ValueError.  Double backward is not supported.  Calls on one operator
+share its workspaces: issue them from one thread (the current stream orders them).
+"""
+from __future__ import annotations
+
+import torch
+from torch.autograd.function import once_differentiable
+
+import bsmr_amd as eng
+
+
+class SparseOperator:
+    def __init__(self, csr: "eng.CSR", alpha=0.3, delta=0.3, mode=eng.COMPUTE_F16, device=0):
+        self.csr = csr
+        self.M, self.N, self.nnz = csr.rows, csr.cols, csr.nnz
+        self.mode = mode
+        self.device = torch.device("cuda", device)
+        self._plan = self._bw = None
+        self.pipeline = eng.Pipeline(csr, alpha=alpha, delta=delta, device=-1)   # host arrays (RPHM) only
+        st, plan = eng.plan_from_arrays(self.M, self.N, self.nnz, self.pipeline.arrays(), device=device)
+        eng._check(st, "bsmr_plan_create")
+        self._plan = plan
+        self._bw = eng.backward_create(self.M, self.N, csr.row_offsets, csr.col_indices,
+                                       row_order=self.pipeline.array("reorderedRows"), device=device)
+
+    def __del__(self):
+        if getattr(self, "_bw", None):
+            eng.backward_destroy(self._bw)
+            self._bw = None
+        if getattr(self, "_plan", None):
+            eng.plan_destroy(self._plan)
+            self._plan = None
+
+    # --- public operators ---
+    def sddmm(self, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+        """P = (A B^T) at S's stored positions: A (M,K) / B (N,K), or (b,M,K) / (b,N,K); P (nnz,) or (b,nnz)"""
+        return _SDDMM.apply(self, A, B)
+
+    def spmm(self, values: torch.Tensor, X: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+        """Y = S_values X (X (N,K) -> Y (M,K)) or, transposed, S_values^T X (X (M,K) -> Y (N,K)); batched with a
+        leading b on values (b,nnz) and X"""
+        return _SpMM.apply(self, values, X, bool(transpose))
+
+    def stats(self) -> dict:
+        return eng.backward_stats(self._bw)
+
+    # --- checks and raw calls (no autograd) ---
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _check(self, t: torch.Tensor, name: str, rows: int, batch):
+        """batch None: either (rows, K) or (b, rows, K); returns (b or None, K)"""
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name}: dtype {t.dtype}, expected torch.float32")
+        if t.device != self.device:
+            raise ValueError(f"{name}: on {t.device}, the operator lives on {self.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: not contiguous")
+        if t.dim() not in (2, 3) or t.shape[-2] != rows:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected ({rows}, K) or (b, {rows}, K)")
+        b = t.shape[0] if t.dim() == 3 else None
+        if batch is not None and b != batch[0]:
+            raise ValueError(f"{name}: shape {tuple(t.shape)} does not match the batch of the other operand")
+        K = t.shape[-1]
+        if K == 0 or K % 32:
+            raise ValueError(f"{name}: K = {K}, expected a positive multiple of 32")
+        if b == 0:
+            raise ValueError(f"{name}: empty batch")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name}: data not 16-byte aligned")
+        return b, K
+
+    def _check_values(self, v: torch.Tensor, b):
+        if not isinstance(v, torch.Tensor):
+            raise ValueError("values: expected a torch.Tensor")
+        want = (self.nnz,) if b is None else (b, self.nnz)
+        if v.dtype != torch.float32 or v.device != self.device or not v.is_contiguous() or tuple(v.shape) != want:
+            raise ValueError(f"values: expected a contiguous float32 tensor of shape {want} on {self.device}, got "
+                             f"{v.dtype} {tuple(v.shape)} on {v.device}")
+
+    def _sddmm(self, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+        b, K = self._check(A, "A", self.M, None)
+        _, K2 = self._check(B, "B", self.N, (b,))
+        if K2 != K:
+            raise ValueError(f"A and B disagree on K ({K} vs {K2})")
+        shape = (self.nnz,) if b is None else (b, self.nnz)
+        P = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if self.nnz == 0:
+            return P
+        if b is None:
+            eng.sddmm(self._plan, K, A.data_ptr(), B.data_ptr(), P.data_ptr(), self.mode, self._stream())
+        else:
+            eng.sddmm_batch(self._plan, K, A.data_ptr(), B.data_ptr(), P.data_ptr(), b, self.mode, self._stream())
+        return P
+
+    def _spmm(self, v: torch.Tensor, X: torch.Tensor, transpose: bool) -> torch.Tensor:
+        rows_x, rows_y = (self.M, self.N) if transpose else (self.N, self.M)
+        b, K = self._check(X, "X", rows_x, None)
+        self._check_values(v, b)
+        Y = torch.empty((rows_y, K) if b is None else (b, rows_y, K), dtype=torch.float32, device=self.device)
+        eng.spmm(self._bw, K, transpose, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream())
+        return Y
+
+    def _sddmm_backward(self, dP, A, B, need_a: bool, need_b: bool):
+        b, K = self._check(A, "A", self.M, None)
+        self._check(B, "B", self.N, (b,))
+        self._check_values(dP, b)
+        dA = torch.empty_like(A) if need_a else None
+        dB = torch.empty_like(B) if need_b else None
+        eng.sddmm_backward(self._bw, K, dP.data_ptr(), A.data_ptr(), B.data_ptr(), dA.data_ptr() if need_a else None,
+                           dB.data_ptr() if need_b else None, b or 1, self._stream())
+        return dA, dB
+
+
+def _grad(t: torch.Tensor) -> torch.Tensor:
+    return t.to(torch.float32).contiguous()
+
+
+class _SDDMM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, op: SparseOperator, A, B):
+        ctx.op = op
+        ctx.save_for_backward(A, B)
+        return op._sddmm(A, B)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dP):
+        op = ctx.op
+        A, B = ctx.saved_tensors
+        need_a, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (need_a or need_b):
+            return None, None, None
+        dA, dB = op._sddmm_backward(_grad(dP), A, B, need_a, need_b)
+        return None, dA, dB
+
+
+class _SpMM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, op: SparseOperator, values, X, transpose: bool):
+        ctx.op, ctx.transpose = op, transpose
+        ctx.save_for_backward(values, X)
+        return op._spmm(values, X, transpose)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dY):
+        op, transpose = ctx.op, ctx.transpose
+        values, X = ctx.saved_tensors
+        dY = _grad(dY)
+        dv = dX = None
+        if ctx.needs_input_grad[1]:
+            dv = op._sddmm(X, dY) if transpose else op._sddmm(dY, X)
+        if ctx.needs_input_grad[2]:
+            dX = op._spmm(values, dY, not transpose)
+        return None, dv, dX, None
+
+
+__all__ = ["SparseOperator"]

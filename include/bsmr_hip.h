@@ -31,6 +31,11 @@
  *                           fp16/bf16 operands skip the per-call conversion
  *   bsmr_sharded_*       <- no reference counterpart (the reference is single-GPU): row-range shards over the
  *                           GPUs of one node, one RCCL gather-v of P per step
+ *   bsmr_backward_*      <- no reference counterpart (the reference has no backward): a per-pattern handle with S's
+ *                           CSR, its transpose and the chunked work lists of dA = S_dP B and dB = S_dP^T A
+ *   bsmr_csr_transpose   <- no reference counterpart: the host transpose bsmr_backward_create uploads
+ *   bsmr_spmm / bsmr_sddmm_backward
+ *                        <- no reference counterpart: Y = S_v X / S_v^T X and the two SDDMM gradients
  *   bsmr_mem_info        <- cudaMemGetInfo in calculateBlockSize (src/rowReordering.cu:1010-1013)
  *   bsmr_dev_alloc / bsmr_dev_free / bsmr_memcpy_h2d / bsmr_memcpy_d2h / bsmr_dev_memset
  *                        <- dev::vector<T> ctor/dtor and h2d()/d2h() (include/devVector.cuh:54-126,
@@ -481,9 +486,10 @@ typedef struct bsmr_sharded_timing {
     float    gather_ms;    /* the gather-v alone: first part leaving to last part delivered               */
 } bsmr_sharded_timing;
 /* Revision of this header's struct layouts (4 = round 4: bsmr_sharded_timing, bsmr_tune_report, bsmr_cluster_stats and
- * bsmr_plan_options grew at their ends).  A caller built against an older revision uses the *_sized entry points for the
- * structs the library writes, or is rebuilt. */
-#define BSMR_ABI_REVISION 4
+ * bsmr_plan_options grew at their ends; 5: the SDDMM backward, bsmr_backward_* / bsmr_spmm / bsmr_sddmm_backward).  A
+ * caller built against an older revision uses the *_sized entry points for the structs the library writes, or is
+ * rebuilt. */
+#define BSMR_ABI_REVISION 5
 int bsmr_abi_revision(void);
 int bsmr_sharded_create(bsmr_sharded **out, const int *devices, uint32_t num_devices,
                         const bsmr_rphm_desc *const *shard_descs, const uint32_t *row_begin,
@@ -495,6 +501,57 @@ int bsmr_sharded_num_entries(const bsmr_sharded *s, uint64_t *total, uint64_t *p
  * shard's rows of A and a replica of B, one warm-up step, `iters` timed steps, download from the root. */
 int bsmr_sharded_sddmm_host(bsmr_sharded *s, uint32_t K, const float *A_host, const float *B_host, float *P_host,
                             int compute_mode, int iters, bsmr_sharded_timing *timing);
+
+/* ---- SDDMM backward (revision 5; no reference counterpart) ----
+ * P = (A B^T) at S's stored positions has the gradients dA = S_dP B and dB = S_dP^T A; attention follows an SDDMM with
+ * Y = S_v X.  All are one gather-and-accumulate: for destination d with list L(d), Y[d,:] = sum_{t in L(d)} v[e(t)] X[s(t),:]
+ * (transpose 0: the rows of S, e(t) = t, s(t) = col_indices[t]; transpose 1: the columns of S, e(t) = csc_to_csr[t],
+ * s(t) = csc_rows[t]).  X and Y are row-major with K contiguous floats per row (the layout of A and B), 16-byte aligned.
+ *
+ * Numerical contract: each destination's sum runs in its list's order (CSR order for rows, ascending row for columns) as
+ * a sequential fp32 fma chain; a list longer than BSMR_BACKWARD_CHUNK is summed chunk by chunk and the partials are added
+ * in chunk order.  No atomics: results are bitwise reproducible call to call, stream to stream, batch to batch and for
+ * any row_order; a destination without entries is exactly 0; |Y - Y_exact| <= (n + 2) u sum|v||x| (n = list length,
+ * u = 2^-24).  The chunk partials live in a workspace of the handle: calls on one handle are ordered by the caller. */
+#define BSMR_BACKWARD_CHUNK 512u   /* entries per work item of a long list (cdna_hip_programming.md, Appendix B) */
+typedef struct bsmr_backward bsmr_backward;
+typedef struct bsmr_backward_stats {
+    uint32_t chunk;               /* BSMR_BACKWARD_CHUNK                                          */
+    uint32_t split_rows;          /* rows (dA destinations) cut into chunks                       */
+    uint32_t split_cols;          /* columns (dB destinations) cut into chunks                    */
+    uint32_t max_row_length;      /* longest row of S                                             */
+    uint32_t max_col_length;      /* longest column of S                                          */
+    uint32_t row_items;           /* work items (whole lists + chunks) of the row direction       */
+    uint32_t col_items;           /* ... of the column direction                                  */
+    uint32_t permute_values;      /* 1: the column direction permutes v into CSC order first (the default;
+                                     BSMR_BACKWARD_PERMUTE=0 at create: read through csc_to_csr)  */
+    uint64_t device_index_bytes;  /* index arrays resident on the device                          */
+    uint64_t workspace_bytes;     /* chunk partials (+ permuted values) reserved so far           */
+} bsmr_backward_stats;
+/* S as host CSR (row_offsets [M+1], col_indices [nnz]; read during the call only).  row_order: the order in which the
+ * row destinations are scheduled (pass the pipeline's reordered_rows, the clustered order); it may list a subset, the
+ * rows it omits follow in natural order.  NULL with num_ordered_rows = 0: natural order.  BSMR_ERR_INVALID_ARG, before
+ * any device call: a duplicate or out-of-range row in row_order, row_offsets[0] != 0, non-monotone row_offsets,
+ * row_offsets[M] != nnz, a column id >= N. */
+int bsmr_backward_create(bsmr_backward **out, int device, uint32_t M, uint32_t N, uint32_t nnz,
+                         const uint32_t *row_offsets, const uint32_t *col_indices,
+                         const uint32_t *row_order, uint32_t num_ordered_rows);
+int bsmr_backward_destroy(bsmr_backward *bw);
+/* Grow the workspace for calls with (K, num_batches) now; calls covered by it allocate nothing (capturable). */
+int bsmr_backward_reserve(bsmr_backward *bw, uint32_t K, uint32_t num_batches);
+/* at most out_size bytes of the statistics are written (the struct only grows at its end) */
+int bsmr_backward_get_stats(const bsmr_backward *bw, bsmr_backward_stats *out, size_t out_size);
+/* Host only, no device: the transpose the handle uploads.  col_offsets [N+1]; csc_rows / csc_to_csr [nnz]: the row and
+ * the CSR index of each entry, column by column, ascending row within a column.  Same argument checks as create. */
+int bsmr_csr_transpose(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t *row_offsets, const uint32_t *col_indices,
+                       uint32_t *col_offsets, uint32_t *csc_rows, uint32_t *csc_to_csr);
+/* Y = S_v X (transpose 0: X N x K, Y M x K) or S_v^T X (transpose 1: X M x K, Y N x K); v in S's CSR order; every
+ * element of Y is overwritten.  Batches as bsmr_sddmm_batch: v [b][nnz], X / Y [b][rows][K], the batch in grid y. */
+int bsmr_spmm(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const float *X_dev, float *Y_dev,
+              uint32_t num_batches, void *stream);
+/* dA = S_dP B (M x K), dB = S_dP^T A (N x K); either output may be NULL: that product is skipped. */
+int bsmr_sddmm_backward(bsmr_backward *bw, uint32_t K, const float *dP_dev, const float *A_dev, const float *B_dev,
+                        float *dA_dev, float *dB_dev, uint32_t num_batches, void *stream);
 
 /* Host operands in, host P out (upload, `iters` timed repetitions after one
  * warm-up, download).  ms_per_iter may be NULL. */

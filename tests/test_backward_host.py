@@ -1,0 +1,120 @@
+"""The host side of the SDDMM backward without a GPU: bsmr_csr_transpose against a stable argsort transpose, and the
+argument checks of bsmr_backward_create / bsmr_spmm / bsmr_sddmm_backward, which reject bad input before any device
+call (include/bsmr_hip.h "SDDMM backward")."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import synth
+
+
+def reference_transpose(rows, cols, ro, ci):
+    ro = np.asarray(ro, dtype=np.int64)
+    ci = np.asarray(ci, dtype=np.int64)
+    row_of = np.repeat(np.arange(rows), np.diff(ro))
+    order = np.argsort(ci, kind="stable")
+    co = np.zeros(cols + 1, dtype=np.int64)
+    np.add.at(co, ci + 1, 1)
+    return np.cumsum(co), row_of[order], order
+
+
+def empty_columns_pattern():
+    rows, cols, ro, ci = synth.random_pattern(60, 90, 700, seed=11)
+    ci = np.where(ci % 3 == 0, ci, ci - ci % 3)       # only every third column is used
+    per_row = [np.unique(ci[ro[r]:ro[r + 1]]) for r in range(rows)]
+    ro2 = np.zeros(rows + 1, dtype=np.uint32)
+    ro2[1:] = np.cumsum([len(p) for p in per_row])
+    return rows, cols, ro2, np.concatenate(per_row).astype(np.uint32)
+
+
+PATTERNS = {
+    "random_empty_rows": lambda: synth.random_pattern(120, 80, 1500, seed=3, empty_rows=17),
+    "empty_columns": empty_columns_pattern,
+    "nnz0": lambda: (5, 7, np.zeros(6, np.uint32), np.zeros(0, np.uint32)),
+    "one_by_one": lambda: (1, 1, np.array([0, 1], np.uint32), np.array([0], np.uint32)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PATTERNS))
+def test_csr_transpose_matches_stable_argsort(engine, name):
+    rows, cols, ro, ci = PATTERNS[name]()
+    co, csc_rows, csc_to_csr = engine.csr_transpose(rows, cols, ro, ci)
+    want_co, want_rows, want_map = reference_transpose(rows, cols, ro, ci)
+    assert np.array_equal(co, want_co)
+    assert np.array_equal(csc_rows, want_rows)
+    assert np.array_equal(csc_to_csr, want_map)
+    if name == "empty_columns":
+        assert (np.diff(co) == 0).sum() >= cols // 2
+    # ascending row within each column (= ascending CSR index)
+    for c in range(cols):
+        seg = csc_to_csr[co[c]:co[c + 1]]
+        assert np.all(np.diff(seg.astype(np.int64)) > 0)
+
+
+def test_csr_transpose_rejects_bad_input(engine):
+    hip = engine.hip()
+    rows, cols, ro, ci = synth.random_pattern(20, 30, 100, seed=5)
+    out = [np.zeros(cols + 1, np.uint32), np.zeros(ci.size, np.uint32), np.zeros(ci.size, np.uint32)]
+    p = engine._ptr
+
+    def call(ro_, ci_, nnz=ci.size, n=cols):
+        return hip.bsmr_csr_transpose(rows, n, nnz, p(ro_), p(ci_), p(out[0]), p(out[1]), p(out[2]))
+
+    assert call(ro, ci) == engine.OK
+    assert hip.bsmr_csr_transpose(rows, cols, ci.size, None, p(ci), p(out[0]), p(out[1]), p(out[2])) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_csr_transpose(rows, cols, ci.size, p(ro), p(ci), None, p(out[1]), p(out[2])) == engine.ERR_INVALID_ARG
+    assert call(ro, ci, n=int(ci.max())) == engine.ERR_INVALID_ARG           # a column id >= N
+    assert call(ro, ci, nnz=ci.size - 1) == engine.ERR_INVALID_ARG          # row_offsets[M] != nnz
+    bad = ro.copy()
+    bad[5] = bad[6] + 1                                                      # non-monotone
+    assert call(bad, ci) == engine.ERR_INVALID_ARG
+
+
+def _no_gpu_or_ok(engine, st, handle):
+    assert st in (engine.OK, engine.ERR_NO_DEVICE), engine.hip().bsmr_strerror(st)
+    if st == engine.OK:
+        engine.backward_destroy(handle)
+
+
+def test_backward_create_rejects_bad_input_before_the_device(engine):
+    rows, cols, ro, ci = synth.random_pattern(50, 40, 400, seed=9, empty_rows=4)
+    create = engine.backward_create_status
+    # valid input reaches the device step: OK with a GPU, NO_DEVICE without one
+    _no_gpu_or_ok(engine, *create(rows, cols, ro, ci))
+    _no_gpu_or_ok(engine, *create(rows, cols, ro, ci, row_order=np.arange(rows)[::-1]))
+    _no_gpu_or_ok(engine, *create(rows, cols, ro, ci, row_order=np.array([7, 3, 11])))     # a subset
+    # row_order: duplicate, out of range
+    assert create(rows, cols, ro, ci, row_order=np.array([1, 2, 1]))[0] == engine.ERR_INVALID_ARG
+    assert create(rows, cols, ro, ci, row_order=np.array([0, rows]))[0] == engine.ERR_INVALID_ARG
+    # a column id >= N, row_offsets[M] != nnz, non-monotone row_offsets
+    assert create(rows, int(ci.max()), ro, ci)[0] == engine.ERR_INVALID_ARG
+    short = ro.copy()
+    short[-1] -= 1
+    assert create(rows, cols, short, ci)[0] == engine.ERR_INVALID_ARG
+    bumpy = ro.copy()
+    bumpy[10] = bumpy[11] + 1
+    assert create(rows, cols, bumpy, ci)[0] == engine.ERR_INVALID_ARG
+    # NULL arguments
+    hip = engine.hip()
+    p = engine._ptr
+    h = C.c_void_p()
+    assert hip.bsmr_backward_create(None, 0, rows, cols, ci.size, p(ro), p(ci), None, 0) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_backward_create(C.byref(h), 0, rows, cols, ci.size, None, p(ci), None, 0) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_backward_create(C.byref(h), 0, rows, cols, ci.size, p(ro), None, None, 0) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_backward_create(C.byref(h), 0, rows, cols, ci.size, p(ro), p(ci), None, 3) == engine.ERR_INVALID_ARG
+    assert not h.value
+
+
+def test_backward_calls_on_null_handle(engine):
+    hip = engine.hip()
+    assert hip.bsmr_spmm(None, 32, 0, None, None, None, 1, None) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_spmm(None, 32, 1, None, None, None, 1, None) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_sddmm_backward(None, 32, None, None, None, None, None, 1, None) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_backward_reserve(None, 32, 1) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_backward_get_stats(None, None, 0) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_backward_destroy(None) == engine.OK
+
+
+def test_abi_revision_is_5(engine):
+    assert engine.hip().bsmr_abi_revision() == 5
