@@ -259,7 +259,9 @@ int bsmr_spmm(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, 
               uint32_t num_batches, void* stream) {
     if (int st = checkBackwardCall(bw, K, num_batches)) return st;
     if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
-    if (!v_dev || !X_dev || !Y_dev || !aligned16(X_dev) || !aligned16(Y_dev)) return BSMR_ERR_INVALID_ARG;
+    // nnz = 0 reads neither v nor X (torch hands out NULL for a zero-element tensor); Y is still written with zeros
+    const bool reads = bw->nnz != 0;
+    if ((reads && (!v_dev || !X_dev)) || !Y_dev || !aligned16(X_dev) || !aligned16(Y_dev)) return BSMR_ERR_INVALID_ARG;
     if (num_batches == 0) return BSMR_OK;
     BSMR_HIP(hipSetDevice(bw->device));
     if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
@@ -269,8 +271,9 @@ int bsmr_spmm(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, 
 int bsmr_sddmm_backward(bsmr_backward* bw, uint32_t K, const float* dP_dev, const float* A_dev, const float* B_dev,
                         float* dA_dev, float* dB_dev, uint32_t num_batches, void* stream) {
     if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    if (!dP_dev || (dA_dev && (!B_dev || !aligned16(B_dev) || !aligned16(dA_dev))) ||
-        (dB_dev && (!A_dev || !aligned16(A_dev) || !aligned16(dB_dev))))
+    const bool reads = bw->nnz != 0;   // as bsmr_spmm: nnz = 0 reads no operand, the outputs are still zeroed
+    if ((reads && !dP_dev) || (dA_dev && ((reads && !B_dev) || !aligned16(B_dev) || !aligned16(dA_dev))) ||
+        (dB_dev && ((reads && !A_dev) || !aligned16(A_dev) || !aligned16(dB_dev))))
         return BSMR_ERR_INVALID_ARG;
     if (num_batches == 0 || (!dA_dev && !dB_dev)) return BSMR_OK;
     BSMR_HIP(hipSetDevice(bw->device));

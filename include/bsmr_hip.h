@@ -546,10 +546,12 @@ int bsmr_backward_get_stats(const bsmr_backward *bw, bsmr_backward_stats *out, s
 int bsmr_csr_transpose(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t *row_offsets, const uint32_t *col_indices,
                        uint32_t *col_offsets, uint32_t *csc_rows, uint32_t *csc_to_csr);
 /* Y = S_v X (transpose 0: X N x K, Y M x K) or S_v^T X (transpose 1: X M x K, Y N x K); v in S's CSR order; every
- * element of Y is overwritten.  Batches as bsmr_sddmm_batch: v [b][nnz], X / Y [b][rows][K], the batch in grid y. */
+ * element of Y is overwritten.  Batches as bsmr_sddmm_batch: v [b][nnz], X / Y [b][rows][K], the batch in grid y.
+ * With nnz = 0 nothing is read: v and X may be NULL (a zero-element tensor's pointer), Y is still all zeros. */
 int bsmr_spmm(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const float *X_dev, float *Y_dev,
               uint32_t num_batches, void *stream);
-/* dA = S_dP B (M x K), dB = S_dP^T A (N x K); either output may be NULL: that product is skipped. */
+/* dA = S_dP B (M x K), dB = S_dP^T A (N x K); either output may be NULL: that product is skipped.  With nnz = 0
+ * dP, A and B may be NULL; the requested outputs are still all zeros. */
 int bsmr_sddmm_backward(bsmr_backward *bw, uint32_t K, const float *dP_dev, const float *A_dev, const float *B_dev,
                         float *dA_dev, float *dB_dev, uint32_t num_batches, void *stream);
 

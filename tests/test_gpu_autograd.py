@@ -159,3 +159,141 @@ def test_bad_inputs_raise_value_error(op):
         op.spmm(v, A)                                     # transpose=False wants N rows
     with pytest.raises(ValueError):
         op.spmm(v, torch.zeros(K, op.N, device=_dev()).T)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# The shipped modes.  SparseOperator's default is COMPUTE_F16; the mode decides the forward SDDMM and so the gradient
+# d values of spmm, but never the fp32 gather of dA / dB / dX, which must equal the backward's twin bit for bit
+# (oracle/spmm_oracle.c; lists from numpy, tests/gather_twin.py).
+# --------------------------------------------------------------------------------------------------------------------
+import ctypes as C  # noqa: E402
+
+from gather_twin import assert_twin, col_lists, gather, row_lists  # noqa: E402
+
+MODES = ("COMPUTE_F16", "COMPUTE_BF16", "COMPUTE_F32")
+ROUND = {"COMPUTE_F16": 2, "COMPUTE_BF16": 3}            # oracle.round_array: fp16 / bf16 RNE
+
+
+@pytest.fixture(scope="module")
+def mode_ops(engine):
+    import bsmr_torch
+    rows, cols, ro, ci = synth.random_pattern(256, 384, 12000, seed=5)
+    csr = engine.CSR.from_arrays(rows, cols, ro, ci)
+    made = {}
+
+    def get(mode):
+        if mode not in made:
+            o = bsmr_torch.SparseOperator(csr, mode=getattr(engine, mode), device=0)
+            o.ro, o.ci = ro.astype(np.uint32), ci.astype(np.uint32)
+            o.row_of = np.repeat(np.arange(rows), np.diff(ro.astype(np.int64)))
+            o.rl, o.cl = row_lists(o.ro, o.ci), col_lists(rows, cols, o.ro, o.ci)
+            made[mode] = o
+        return made[mode]
+
+    yield get
+    made.clear()
+
+
+def _wide(rng, shape, lo, hi):
+    """+-m 2^e, full 24-bit m, e in [lo, hi]"""
+    m = rng.integers(1 << 23, 1 << 24, size=shape).astype(np.float64)
+    e = rng.integers(lo, hi + 1, size=shape) - 23
+    return (rng.choice([-1.0, 1.0], size=shape) * np.ldexp(m, e)).astype(np.float32)
+
+
+def _leaf(a, requires_grad=True):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(_dev()).requires_grad_(requires_grad)
+
+
+@pytest.mark.parametrize("batch", [None, 2])
+@pytest.mark.parametrize("mode", MODES)
+def test_sddmm_gradients_equal_the_twin_in_every_mode(mode_ops, oracle, mode, batch):
+    """'exact fp32 products of the given operands in every mode': A.grad and B.grad are the twin's bits"""
+    op = mode_ops(mode)
+    K = 96
+    rng = np.random.default_rng(len(mode) + (batch or 0))
+    lead = () if batch is None else (batch,)
+    A, B = _wide(rng, lead + (op.M, K), -12, 12), _wide(rng, lead + (op.N, K), -12, 12)
+    G = _wide(rng, lead + (op.nnz,), -12, 12)
+    tA, tB = _leaf(A), _leaf(B)
+    (op.sddmm(tA, tB) * _leaf(G, False)).sum().backward()
+    gA, gB = tA.grad.cpu().numpy(), tB.grad.cpu().numpy()
+    for b in range(batch or 1):
+        sel = (lambda x: x) if batch is None else (lambda x, b=b: x[b])
+        assert_twin(sel(gA), gather(oracle, op.rl, sel(G), sel(B)), f"{mode} A.grad batch {b}")
+        assert_twin(sel(gB), gather(oracle, op.cl, sel(G), sel(A)), f"{mode} B.grad batch {b}")
+
+
+def _entry_paths(engine, op, K):
+    """per CSR entry: True where this mode's forward SDDMM reads rounded operands (dense path, or a low-precision
+    residue)"""
+    mode = op.mode
+    if mode == engine.COMPUTE_F32:
+        return np.zeros(op.nnz, dtype=bool)
+    flags = np.zeros(op.nnz, dtype=np.uint8)
+    assert engine.hip().bsmr_plan_dense_flags(op._plan, flags.ctypes.data_as(C.c_void_p)) == engine.OK
+    lanes, lowp = C.c_uint32(0), C.c_uint32(0)
+    assert engine.hip().bsmr_plan_sparse_choice(op._plan, K, mode, C.byref(lanes), C.byref(lowp)) == engine.OK
+    return flags.astype(bool) | bool(lowp.value)
+
+
+@pytest.mark.parametrize("scale", [1.0, 2.0 ** -20], ids=["unit", "grad-2^-20"])
+@pytest.mark.parametrize("transpose", [False, True])
+@pytest.mark.parametrize("mode", MODES)
+def test_spmm_gradients_in_every_mode(engine, mode_ops, oracle, mode, transpose, scale):
+    """X.grad = spmm(values, dY) is the twin's bits.  d values = the plan's SDDMM of (dY, X) in the operator's mode: an
+    entry that the mode rounds is within the forward bound (K/16 + 8) 2^-23 sum|a~||b~| of the fp64 product of the
+    rounded operands a~, b~ (oracle.round_array); an fp32 entry within (K + 2) u sum|a||b| of the fp64 product.  With
+    dY scaled by 2^-20 most of dY is an fp16 subnormal or zero: this pins what that model gives there."""
+    op = mode_ops(mode)
+    K = 64
+    rng = np.random.default_rng(7 + transpose)
+    rows_x, rows_y = (op.M, op.N) if transpose else (op.N, op.M)
+    v = rng.uniform(-1, 1, op.nnz).astype(np.float32)
+    X = rng.uniform(-1, 1, (rows_x, K)).astype(np.float32)
+    H = (rng.uniform(-1, 1, (rows_y, K)) * scale).astype(np.float32)
+    tv, tX = _leaf(v), _leaf(X)
+    (op.spmm(tv, tX, transpose=transpose) * _leaf(H, False)).sum().backward()
+    # X.grad = S_v^T H (transpose False) or S_v H (True)
+    assert_twin(tX.grad.cpu().numpy(), gather(oracle, op.rl if transpose else op.cl, v, H), f"{mode} X.grad")
+    # d values[t] = a[row(t)] . b[col(t)] with (a, b) = (H, X), transposed (X, H)
+    a, b = (X, H) if transpose else (H, X)
+    r, c = op.row_of, op.ci.astype(np.int64)
+    got = tv.grad.cpu().numpy().astype(np.float64)
+    rounded = _entry_paths(engine, op, K)
+    exact = (a[r].astype(np.float64) * b[c]).sum(1)
+    mag = (np.abs(a[r].astype(np.float64)) * np.abs(b[c])).sum(1)
+    s = ~rounded
+    assert (np.abs(got[s] - exact[s]) <= (K + 2) * U * mag[s] + 1e-45).all(), (mode, "fp32 entries")
+    if mode in ROUND:
+        assert rounded.any()
+        ar, br = oracle.round_array(ROUND[mode], a), oracle.round_array(ROUND[mode], b)
+        model = (ar[r].astype(np.float64) * br[c]).sum(1)
+        mag_r = (np.abs(ar[r].astype(np.float64)) * np.abs(br[c])).sum(1)
+        err = np.abs(got[rounded] - model[rounded])
+        assert (err <= (K / 16 + 8) * 2.0 ** -23 * mag_r[rounded] + 1e-45).all(), (mode, "rounded entries", err.max())
+    else:
+        assert not rounded.any()
+
+
+def test_empty_pattern(engine):
+    """a pattern without stored entries: spmm gives zeros, and the gradients of spmm and sddmm are zeros (values of
+    zero elements come with a NULL data pointer)"""
+    import bsmr_torch
+    M, N, K = 6, 9, 64
+    csr = engine.CSR.from_arrays(M, N, np.zeros(M + 1, np.uint32), np.zeros(0, np.uint32))
+    op = bsmr_torch.SparseOperator(csr, device=0)
+    for transpose in (False, True):
+        rows_x, rows_y = (M, N) if transpose else (N, M)
+        v = torch.zeros(0, device=_dev(), requires_grad=True)
+        X = torch.rand(rows_x, K, device=_dev(), requires_grad=True)
+        Y = op.spmm(v, X, transpose=transpose)
+        assert Y.shape == (rows_y, K) and (Y == 0).all()
+        (Y * torch.rand(rows_y, K, device=_dev())).sum().backward()
+        assert v.grad.shape == (0,) and (X.grad == 0).all()
+    A = torch.rand(M, K, device=_dev(), requires_grad=True)
+    B = torch.rand(N, K, device=_dev(), requires_grad=True)
+    P = op.sddmm(A, B)
+    assert P.shape == (0,)
+    P.sum().backward()
+    assert (A.grad == 0).all() and (B.grad == 0).all()
