@@ -1371,8 +1371,12 @@ int launchSweep(const bsmr_plan* p, uint32_t K, const void* A, const void* B, fl
 inline bool gemmServesK(uint32_t K) { return K == 64 || K == 128 || K == 256 || K == 512; }
 // ... or, for K <= 128, the caller's fp32 operands rounded in the kernel (slices of 32 k; K = 32 is the streaming kernel's)
 inline bool gemmFp32ServesK(uint32_t K) { return K == 64 || K == 128; }
+// ... and P stored through one buffer resource of num_records = 0xFFFFFFFC at byte offset 4 x CSR index (gemmStoreEntry):
+// the hardware drops a store whose offset + 4 exceeds num_records, so the largest index it can write is 2^30 - 2 and the
+// index itself, a uint32 shifted left by 2, wraps from 2^30 on.  4 nnz <= 0xFFFFFFFC, i.e. nnz < 2^30, bounds every index.
 inline bool gemmFits(const bsmr_plan* p, uint32_t K, uint32_t elemBytes = 2) {
-    return (uint64_t)p->M * K * elemBytes < (1ull << 32) && (uint64_t)p->N * K * elemBytes < (1ull << 32);
+    return (uint64_t)p->M * K * elemBytes < (1ull << 32) && (uint64_t)p->N * K * elemBytes < (1ull << 32) &&
+           (uint64_t)p->nnz * 4u <= 0xFFFFFFFCull;
 }
 inline bool gemmWanted(const bsmr_plan* p, uint32_t K) {
     return p->useGemm && gemmServesK(K) && gemmFits(p, K) && p->hostDense.entries() != 0;

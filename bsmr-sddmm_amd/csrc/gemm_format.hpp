@@ -118,6 +118,8 @@ inline int packGemm(const HostDense& hd, uint32_t PM, uint32_t NB, GemmFormatHos
     out.PM = PM; out.NB = NB; out.numGroups = G; out.numStrips = S; out.passes = Q;
     if (P == 0 || NCB == 0 || hd.entries() == 0) return BSMR_OK;
     if ((uint64_t)G * S > 0x3FFFFFFFull || hd.entries() > 0xFFFFFFF0ull) return BSMR_ERR_INVALID_ARG;
+    // the kernels store P at byte offset 4 x CSR index below num_records = 0xFFFFFFFC (gemmStoreEntry): nnz < 2^30
+    if ((uint64_t)hd.nnz * 4u > 0xFFFFFFFCull) return BSMR_ERR_INVALID_ARG;
     out.panelRows.assign((size_t)G * TM, hd.panelRows.empty() ? 0u : hd.panelRows[0]);
     // 0a. the place of every row: rowPos[panel * 16 + row in panel] = group * TM + row in macro-tile
     std::vector<uint32_t> rowPos((size_t)P * 16);

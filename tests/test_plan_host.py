@@ -236,7 +236,7 @@ def gemmcheck(engine):
     lib.plancheck_gemm.restype = C.c_int
     lib.plancheck_gemm.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
 
-    def run(rows, cols, ro, ci, alpha, delta, panels, blocks, balance=1):
+    def run(rows, cols, ro, ci, alpha, delta, panels, blocks, balance=1, nnz=None):
         csr = engine.CSR.from_arrays(rows, cols, ro, ci)
         pipe = engine.Pipeline(csr, alpha=alpha, delta=delta, device=-1)
         arrays = pipe.arrays()
@@ -244,7 +244,7 @@ def gemmcheck(engine):
                 ("reorderedRows", "denseCols", "blockOffsets", "blockValues", "sparseValueOffsets",
                  "sparseValues", "sparseRelativeRows", "sparseColIndices")}
         d = engine.RphmDesc()
-        d.M, d.N, d.nnz = rows, cols, csr.nnz
+        d.M, d.N, d.nnz = rows, cols, csr.nnz if nnz is None else nnz   # (nnz: a larger P than the pattern's)
         d.num_nonzero_rows = keep["reorderedRows"].size
         d.num_row_panels = keep["blockOffsets"].size - 1
         cast = lambda a: a.ctypes.data_as(engine.u32p)
@@ -275,6 +275,21 @@ def test_gemm_format_lists_every_dense_entry_once(gemmcheck, panels, blocks):
         assert r["groups"] == -(-21 // panels) and r["strips"] == -(-94 // blocks)
         assert r["items"] <= r["groups"] * r["strips"] and r["full_grid"] == (r["items"] == r["groups"] * r["strips"])
         assert r["tiles"] == r["items"] * panels * blocks
+
+
+@pytest.mark.parametrize("nnz", [1 << 30, (1 << 30) + (1 << 15), 0xFFFFFFFF])
+def test_gemm_format_refuses_p_past_the_store_range(gemmcheck, nnz):
+    """denseGemm stores P at byte offset 4 x CSR index below num_records = 0xFFFFFFFC: packGemm refuses a plan of 2^30
+    entries or more (BSMR_ERR_INVALID_ARG, 200 + 1 from plancheck_gemm) before it packs anything.  The same dense
+    pattern packs at its own nnz.  (The largest plan it serves, 2^30 - 1 entries, runs on the device in
+    tests/test_gpu_extents.py: plancheck_gemm's brute-force reading would need 8 GiB here.)"""
+    rows, cols = 64, 64
+    ro = np.arange(rows + 1, dtype=np.uint32) * cols
+    ci = np.tile(np.arange(cols, dtype=np.uint32), rows)
+    rc, r = gemmcheck(rows, cols, ro, ci, 0.3, 0.0, 8, 8)
+    assert rc == 0 and r["entries"] == ci.size, (rc, r)
+    rc, _ = gemmcheck(rows, cols, ro, ci, 0.3, 0.0, 8, 8, nnz=nnz)
+    assert rc == 201, rc
 
 
 def test_gemm_format_takes_unsorted_rows_full_tiles_and_empty_macro_tiles(gemmcheck):
