@@ -15,6 +15,7 @@
 struct bsmr_backward {
     int device = 0;
     uint32_t M = 0, N = 0, nnz = 0;
+    uint32_t* rowOffsets = nullptr;   // [M+1]  S's row offsets (the softmax, csrc/softmax_capi.hpp)
     uint32_t* colIndices = nullptr;   // [nnz]  s(t) of the row direction
     uint32_t* cscRows = nullptr;      // [nnz]  s(t) of the column direction
     uint32_t* cscToCsr = nullptr;     // [nnz]  e(t) of the column direction
@@ -28,7 +29,7 @@ struct bsmr_backward {
     uint64_t workFloats = 0;
 
     ~bsmr_backward() {
-        for (void* p : {(void*)colIndices, (void*)cscRows, (void*)cscToCsr, (void*)items[0], (void*)items[1],
+        for (void* p : {(void*)rowOffsets, (void*)colIndices, (void*)cscRows, (void*)cscToCsr, (void*)items[0], (void*)items[1],
                         (void*)splits[0], (void*)splits[1], (void*)work})
             if (p) (void)hipFree(p);
     }
@@ -209,6 +210,7 @@ int bsmr_backward_create(bsmr_backward** out, int device, uint32_t M, uint32_t N
         buildItems(co.data(), N, cols, items[1], splits[1], bw->numSlots[1], bw->maxLen[1]);
         if (items[0].size() > 0xFFFFFFFFull || items[1].size() > 0xFFFFFFFFull) return BSMR_ERR_INVALID_ARG;
         uint64_t& bytes = bw->indexBytes;
+        if (int st = upload(bw->rowOffsets, std::vector<uint32_t>(row_offsets, row_offsets + M + 1u), bytes)) return st;
         if (int st = upload(bw->colIndices, ci, bytes)) return st;
         if (int st = upload(bw->cscRows, cscRows, bytes)) return st;
         if (int st = upload(bw->cscToCsr, cscToCsr, bytes)) return st;

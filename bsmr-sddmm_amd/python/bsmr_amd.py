@@ -208,6 +208,9 @@ HIP_SYMBOLS = {
     "bsmr_spmm": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsmr_sddmm_backward": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint32, C.c_void_p]),
+    "bsmr_sparse_softmax": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bsmr_sparse_softmax_backward": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                               C.c_void_p]),
 }
 
 HOST_SYMBOLS = {
@@ -721,3 +724,14 @@ def sddmm_backward(bw, K: int, dP_ptr: int, A_ptr: int, B_ptr: int, dA_ptr, dB_p
     """dA = S_dP B, dB = S_dP^T A; dA_ptr / dB_ptr None (or 0) skips that product"""
     _check(hip().bsmr_sddmm_backward(bw, K, dP_ptr, A_ptr, B_ptr, dA_ptr or None, dB_ptr or None, num_batches, stream),
            "bsmr_sddmm_backward")
+
+
+def sparse_softmax(bw, scale: float, X_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0):
+    """Y = the row softmax of fl32(scale * X) over S's pattern (values in CSR order; Y may be X)"""
+    _check(hip().bsmr_sparse_softmax(bw, scale, X_ptr or None, Y_ptr or None, num_batches, stream), "bsmr_sparse_softmax")
+
+
+def sparse_softmax_backward(bw, scale: float, Y_ptr: int, dY_ptr: int, dX_ptr: int, num_batches: int = 1, stream: int = 0):
+    """dX = (Y * (dY - rowsum(Y * dY))) * scale (dX may be dY)"""
+    _check(hip().bsmr_sparse_softmax_backward(bw, scale, Y_ptr or None, dY_ptr or None, dX_ptr or None, num_batches,
+                                              stream), "bsmr_sparse_softmax_backward")

@@ -2,19 +2,25 @@
 
     op = SparseOperator(csr)                 # pipeline (clustered rows), SDDMM plan, backward handle
     P = op.sddmm(A, B)                       # P[t] = A[row(t)] . B[col(t)]           (nnz,) or (b, nnz)
+    W = op.softmax(P, scale)                 # W = softmax of scale * P over each row of S   (nnz,) or (b, nnz)
     Y = op.spmm(values, X)                   # Y = S_values X     (transpose=True: S_values^T X)
+    O = op.attention(Q, Kt, V)               # spmm(softmax(sddmm(Q, Kt), K**-0.5), V)
 
-Both are torch.autograd.Functions whose backward runs on the engine (bsmr_sddmm_backward, bsmr_spmm, bsmr_sddmm):
-    sddmm:  dA = S_dP B,  dB = S_dP^T A      (exact fp32 products of the given operands in every mode: the forward's
+All are torch.autograd.Functions whose backward runs on the engine (bsmr_sddmm_backward, bsmr_spmm, bsmr_sddmm,
+bsmr_sparse_softmax_backward), attention by composing the other three:
+    sddmm:    dA = S_dP B,  dB = S_dP^T A    (exact fp32 products of the given operands in every mode: the forward's
                                               operand rounding is treated as straight-through)
-    spmm:   d values = sddmm(dY, X)  (transposed: sddmm(X, dY)),  dX = spmm(values, dY, not transpose)
-so SDDMM -> softmax in torch -> SpMM, the usual sparse-attention layer, trains on the engine end to end.
+    softmax:  dX = (W * (dW - rowsum(W * dW))) * scale   (bsmr_sparse_softmax_backward: bitwise reproducible)
+    spmm:     d values = sddmm(dY, X)  (transposed: sddmm(X, dY)),  dX = spmm(values, dY, not transpose)
+so SDDMM -> softmax -> SpMM, the usual sparse-attention layer, trains on the engine end to end.
 
 Every call runs on torch.cuda.current_stream(device).  Operands are fp32, contiguous, on the operator's device, with
 K a positive multiple of 32; anything else raises ValueError.  Double backward is not supported.  Calls on one operator
 share its workspaces: issue them from one thread (the current stream orders them).
 """
 from __future__ import annotations
+
+import math
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -53,6 +59,19 @@ class SparseOperator:
         """Y = S_values X (X (N,K) -> Y (M,K)) or, transposed, S_values^T X (X (M,K) -> Y (N,K)); batched with a
         leading b on values (b,nnz) and X"""
         return _SpMM.apply(self, values, X, bool(transpose))
+
+    def softmax(self, values: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+        """the softmax of scale * values over each row of S (values (nnz,) or (b, nnz) in S's CSR order): a row whose
+        entries are all -inf gives zeros, a NaN or +inf makes its row NaN, rows without entries hold nothing"""
+        return _Softmax.apply(self, values, scale)
+
+    def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None) -> torch.Tensor:
+        """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
+        positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row."""
+        P = self.sddmm(Q, Kt)
+        if scale is None:
+            scale = Q.shape[-1] ** -0.5
+        return self.spmm(self.softmax(P, scale), V)
 
     def stats(self) -> dict:
         return eng.backward_stats(self._bw)
@@ -116,6 +135,34 @@ class SparseOperator:
         eng.spmm(self._bw, K, transpose, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream())
         return Y
 
+    def _softmax_args(self, v: torch.Tensor, scale):
+        if not isinstance(v, torch.Tensor):
+            raise ValueError("values: expected a torch.Tensor")
+        b = v.shape[0] if v.dim() == 2 else None
+        self._check_values(v, b)
+        if b == 0:
+            raise ValueError("values: empty batch")
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"scale: {scale!r} is not a number") from None
+        if not math.isfinite(scale):
+            raise ValueError(f"scale: {scale} is not finite")
+        return b, scale
+
+    def _softmax(self, v: torch.Tensor, scale: float) -> torch.Tensor:
+        b, scale = self._softmax_args(v, scale)
+        Y = torch.empty_like(v)
+        eng.sparse_softmax(self._bw, scale, v.data_ptr(), Y.data_ptr(), b or 1, self._stream())
+        return Y
+
+    def _softmax_backward(self, Y: torch.Tensor, dY: torch.Tensor, scale: float) -> torch.Tensor:
+        b, scale = self._softmax_args(Y, scale)
+        self._check_values(dY, b)
+        dX = torch.empty_like(dY)
+        eng.sparse_softmax_backward(self._bw, scale, Y.data_ptr(), dY.data_ptr(), dX.data_ptr(), b or 1, self._stream())
+        return dX
+
     def _sddmm_backward(self, dP, A, B, need_a: bool, need_b: bool):
         b, K = self._check(A, "A", self.M, None)
         self._check(B, "B", self.N, (b,))
@@ -169,6 +216,23 @@ class _SpMM(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             dX = op._spmm(values, dY, not transpose)
         return None, dv, dX, None
+
+
+class _Softmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, op: SparseOperator, values, scale):
+        Y = op._softmax(values, scale)
+        ctx.op, ctx.scale = op, float(scale)
+        ctx.save_for_backward(Y)
+        return Y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dY):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None
+        (Y,) = ctx.saved_tensors
+        return None, ctx.op._softmax_backward(Y, _grad(dY), ctx.scale), None
 
 
 __all__ = ["SparseOperator"]

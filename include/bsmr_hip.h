@@ -36,6 +36,8 @@
  *   bsmr_csr_transpose   <- no reference counterpart: the host transpose bsmr_backward_create uploads
  *   bsmr_spmm / bsmr_sddmm_backward
  *                        <- no reference counterpart: Y = S_v X / S_v^T X and the two SDDMM gradients
+ *   bsmr_sparse_softmax / bsmr_sparse_softmax_backward
+ *                        <- no reference counterpart: the row softmax over S's pattern and its gradient
  *   bsmr_mem_info        <- cudaMemGetInfo in calculateBlockSize (src/rowReordering.cu:1010-1013)
  *   bsmr_dev_alloc / bsmr_dev_free / bsmr_memcpy_h2d / bsmr_memcpy_d2h / bsmr_dev_memset
  *                        <- dev::vector<T> ctor/dtor and h2d()/d2h() (include/devVector.cuh:54-126,
@@ -554,6 +556,29 @@ int bsmr_spmm(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, 
  * dP, A and B may be NULL; the requested outputs are still all zeros. */
 int bsmr_sddmm_backward(bsmr_backward *bw, uint32_t K, const float *dP_dev, const float *A_dev, const float *B_dev,
                         float *dA_dev, float *dB_dev, uint32_t num_batches, void *stream);
+
+/* ---- Sparse row softmax (revision 5, added without any layout change; no reference counterpart) ----
+ * The middle step of sparse attention (SDDMM -> softmax -> SpMM) on the same handle: values in S's CSR order, row r
+ * owning positions [row_offsets[r], row_offsets[r+1]).  Per row, each step one IEEE-rounded fp32 operation:
+ *   forward   z_t = fl32(scale x_t);  m = max_t z_t;  e_t = expf(z_t - m) (the accurate expf);  s = sum_t e_t;
+ *             y_t = e_t / s (IEEE division)
+ *   backward  g = sum_t y_t dY_t;  dX_t = fl32(fl32(y_t fl32(dY_t - g)) scale)
+ * Summation order of s and g: that of bsmr_spmm's rows - a sequential fp32 chain in CSR order from +0 (s: s + e_t, g:
+ * fmaf(y_t, dY_t, g)), a row longer than BSMR_BACKWARD_CHUNK summed chunk by chunk with the partials added in chunk
+ * order.  It depends on the pattern alone: results are bitwise reproducible call to call, stream to stream, batch to
+ * batch, in place or not, and for any row_order.  The backward is exactly that twin (oracle_gather_twin at K = 1).
+ * Special values: a row whose entries are all -inf (m = -inf) gives exact zeros (and, with finite dY, a zero gradient);
+ * any other -inf entry gives exactly 0; a NaN or +inf z anywhere in a row makes that whole row NaN and no other; a row
+ * with one finite entry gives exactly 1; rows without entries are not touched.
+ * Forward bound against fp64 over the same z (u = 2^-24, n the row length, Z_r = max_j |z_j - m|):
+ *   |y_t - y64_t| <= (n + 6 + |z_t - m| + Z_r) u y64_t + (n + 2) 2^-126,   |sum_t y_t - 1| <= (n + 6) u + (n + 2) 2^-126.
+ * Batches: values [b][nnz], the batch in grid y (b <= 65535).  Y may alias X, dX may alias dY.  num_batches = 0 is a
+ * no-op; a NULL handle, a non-finite scale or a NULL array with nnz > 0 is BSMR_ERR_INVALID_ARG; with nnz = 0 the arrays
+ * may be NULL.  Neither call allocates (no workspace): both can be captured in a graph. */
+int bsmr_sparse_softmax(bsmr_backward *bw, float scale, const float *X_dev, float *Y_dev,
+                        uint32_t num_batches, void *stream);
+int bsmr_sparse_softmax_backward(bsmr_backward *bw, float scale, const float *Y_dev, const float *dY_dev,
+                                 float *dX_dev, uint32_t num_batches, void *stream);
 
 /* Host operands in, host P out (upload, `iters` timed repetitions after one
  * warm-up, download).  ms_per_iter may be NULL. */
