@@ -112,8 +112,6 @@ int checkBackwardCall(const bsmr_backward* bw, uint32_t K, uint32_t nb) {
     return BSMR_OK;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.
 int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const float* X, float* Y, uint32_t nb, hipStream_t s) {
     const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
@@ -263,7 +261,8 @@ int bsmr_spmm(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, 
     if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
     // nnz = 0 reads neither v nor X (torch hands out NULL for a zero-element tensor); Y is still written with zeros
     const bool reads = bw->nnz != 0;
-    if ((reads && (!v_dev || !X_dev)) || !Y_dev || !aligned16(X_dev) || !aligned16(Y_dev)) return BSMR_ERR_INVALID_ARG;
+    if ((reads && (!v_dev || !X_dev)) || !Y_dev || !aligned4(v_dev) || !aligned16(X_dev) || !aligned16(Y_dev))
+        return BSMR_ERR_INVALID_ARG;
     if (num_batches == 0) return BSMR_OK;
     BSMR_HIP(hipSetDevice(bw->device));
     if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
@@ -274,7 +273,7 @@ int bsmr_sddmm_backward(bsmr_backward* bw, uint32_t K, const float* dP_dev, cons
                         float* dA_dev, float* dB_dev, uint32_t num_batches, void* stream) {
     if (int st = checkBackwardCall(bw, K, num_batches)) return st;
     const bool reads = bw->nnz != 0;   // as bsmr_spmm: nnz = 0 reads no operand, the outputs are still zeroed
-    if ((reads && !dP_dev) || (dA_dev && ((reads && !B_dev) || !aligned16(B_dev) || !aligned16(dA_dev))) ||
+    if ((reads && !dP_dev) || !aligned4(dP_dev) || (dA_dev && ((reads && !B_dev) || !aligned16(B_dev) || !aligned16(dA_dev))) ||
         (dB_dev && ((reads && !A_dev) || !aligned16(A_dev) || !aligned16(dB_dev))))
         return BSMR_ERR_INVALID_ARG;
     if (num_batches == 0 || (!dA_dev && !dB_dev)) return BSMR_OK;

@@ -1773,6 +1773,19 @@ int checkCall(const bsmr_plan* p, uint32_t K, const void* A, const void* B, cons
     return BSMR_OK;
 }
 
+// Alignment of device pointers (include/bsmr_hip.h "Alignment"): the operand matrices and their 16-bit copies move 16
+// bytes at a time (global_load_dwordx4, LDS-DMA of 16 bytes, the conversion pass's 16-byte stores, float4 in the
+// backward); value arrays are read and written one float at a time.
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+// checkCall for the entry points whose A, B and P are device memory (bsmr_sddmm_host hands checkCall host pointers, which
+// carry no requirement): refused before any device work
+int checkDeviceCall(const bsmr_plan* p, uint32_t K, const void* A, const void* B, const void* P, int mode) {
+    if (int st = checkCall(p, K, A, B, P, mode)) return st;
+    return aligned16(A) && aligned16(B) && aligned4(P) ? BSMR_OK : BSMR_ERR_INVALID_ARG;
+}
+
 // all-sparse plan, residue entries x K large enough to repay a conversion pass over B (and the kernel boundary
 // after it): B alone is converted and the residue kernel rounds A's rows while it stages them in LDS
 inline bool convertsBOnly(const bsmr_plan* p, uint32_t K, uint32_t batches = 1) {
@@ -2733,7 +2746,7 @@ int bsmr_plan_reserve(bsmr_plan* plan, uint32_t K) {
 int bsmr_sddmm(bsmr_plan* plan, uint32_t K, const float* A, const float* B, float* P, int mode,
                void* stream) {
     plan = servedFor(plan, K, mode);
-    int st = checkCall(plan, K, A, B, P, mode);
+    int st = checkDeviceCall(plan, K, A, B, P, mode);
     if (st != BSMR_OK) return st;
     BSMR_HIP(hipSetDevice(plan->device));
     if ((st = prepareDense(plan, K, mode)) != BSMR_OK) return st;
@@ -2744,7 +2757,7 @@ int bsmr_sddmm(bsmr_plan* plan, uint32_t K, const float* A, const float* B, floa
 int bsmr_sddmm_batch(bsmr_plan* plan, uint32_t K, const float* A, const float* B, float* P, uint32_t num_batches,
                      int mode, void* stream) {
     plan = servedFor(plan, K, mode);
-    int st = checkCall(plan, K, A, B, P, mode);
+    int st = checkDeviceCall(plan, K, A, B, P, mode);
     if (st != BSMR_OK) return st;
     if (num_batches == 0) return BSMR_OK;
     if (num_batches > 65535u || (uint64_t)K * num_batches > 0xFFFFFFFFull) return BSMR_ERR_INVALID_ARG;
@@ -2765,7 +2778,7 @@ int bsmr_sddmm_batch(bsmr_plan* plan, uint32_t K, const float* A, const float* B
 
 int bsmr_batched_transpose(uint32_t width, uint32_t height, uint32_t num_batches, const float* in_dev, float* out_dev,
                            void* stream) {
-    if (!in_dev || !out_dev) return BSMR_ERR_INVALID_ARG;
+    if (!in_dev || !out_dev || !aligned4(in_dev) || !aligned4(out_dev)) return BSMR_ERR_INVALID_ARG;
     if (width == 0 || height == 0 || num_batches == 0) return BSMR_OK;
     if (num_batches > 65535u || (height + 31) / 32 > 65535u) return BSMR_ERR_INVALID_ARG;
     hipLaunchKernelGGL(bsmr::batchedTranspose, dim3((width + 31) / 32, (height + 31) / 32, num_batches),
@@ -2780,6 +2793,7 @@ int bsmr_convert_operands(bsmr_plan* plan, uint32_t K, const float* A, const flo
     if (!plan || !A || !B || !A16 || !B16) return BSMR_ERR_INVALID_ARG;
     if (K == 0 || (K & 31u)) return BSMR_ERR_UNSUPPORTED_K;
     if (mode != BSMR_COMPUTE_F16 && mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
+    if (!aligned16(A) || !aligned16(B) || !aligned16(A16) || !aligned16(B16)) return BSMR_ERR_INVALID_ARG;
     BSMR_HIP(hipSetDevice(plan->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     return mode == BSMR_COMPUTE_F16
@@ -2795,6 +2809,8 @@ int bsmr_sddmm_lowp(bsmr_plan* plan, uint32_t K, const void* A16, const void* B1
     if (mode != BSMR_COMPUTE_F16 && mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
     const bool residueLowp = plan->sparseLowp && plan->convertPass;
     if (plan->numSparseItems && !residueLowp && (!A || !B)) return BSMR_ERR_INVALID_ARG;  // fp32 residue
+    // (A and B may be NULL when nothing reads them; NULL is aligned)
+    if (!aligned16(A16) || !aligned16(B16) || !aligned16(A) || !aligned16(B) || !aligned4(P)) return BSMR_ERR_INVALID_ARG;
     BSMR_HIP(hipSetDevice(plan->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int pst = prepareDense(plan, K, mode)) return pst;
@@ -2814,7 +2830,7 @@ int bsmr_sddmm_lowp(bsmr_plan* plan, uint32_t K, const void* A16, const void* B1
 int bsmr_sddmm_timed(bsmr_plan* plan, uint32_t K, const float* A, const float* B, float* P, int mode,
                      void* stream, int warmup, int iters, bsmr_timing* out) {
     plan = servedFor(plan, K, mode);
-    int st = checkCall(plan, K, A, B, P, mode);
+    int st = checkDeviceCall(plan, K, A, B, P, mode);
     if (st != BSMR_OK) return st;
     if (!out || iters <= 0 || warmup < 0) return BSMR_ERR_INVALID_ARG;
     BSMR_HIP(hipSetDevice(plan->device));
@@ -2855,7 +2871,7 @@ namespace {
 int tuneEngines(bsmr_plan* plan, uint32_t K, const float* A, const float* B, float* P, int mode, void* stream,
                 bsmr_tune_report* report) {
     constexpr float kTuneMargin = 0.98f;   // what the untuned rules choose stays unless an alternative is 2 % faster
-    int st = checkCall(plan, K, A, B, P, mode);
+    int st = checkDeviceCall(plan, K, A, B, P, mode);
     if (st != BSMR_OK) return st;
     if (!plan->tunable) return BSMR_ERR_INVALID_ARG;
     bsmr_tune_report r{};

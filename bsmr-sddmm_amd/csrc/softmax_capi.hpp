@@ -12,11 +12,11 @@
 namespace {
 
 // the checks of both calls, before any device call: `arrays` (the call's value arrays) may be NULL only with nnz = 0
+// and are whole floats (4-byte aligned)
 int checkSoftmaxCall(const bsmr_backward* bw, float scale, std::initializer_list<const void*> arrays, uint32_t nb) {
     if (!bw || !std::isfinite(scale) || nb > 65535u) return BSMR_ERR_INVALID_ARG;
-    if (bw->nnz)
-        for (const void* p : arrays)
-            if (!p) return BSMR_ERR_INVALID_ARG;
+    for (const void* p : arrays)
+        if ((bw->nnz && !p) || !aligned4(p)) return BSMR_ERR_INVALID_ARG;
     return BSMR_OK;
 }
 

@@ -59,7 +59,7 @@ extern "C" {
 #endif
 
 #define BSMR_OK                 0
-#define BSMR_ERR_INVALID_ARG    1  /* NULL pointer, inconsistent sizes            */
+#define BSMR_ERR_INVALID_ARG    1  /* NULL or misaligned pointer, inconsistent sizes */
 #define BSMR_ERR_NO_DEVICE      2  /* no usable gfx950 device / bad device index  */
 #define BSMR_ERR_HIP            3  /* a HIP runtime call failed (see last error)  */
 #define BSMR_ERR_UNSUPPORTED_K  4  /* K == 0 or K not a multiple of 32            */
@@ -432,6 +432,21 @@ int bsmr_plan_dense_flags(const bsmr_plan *plan, uint8_t *flags_host);
  * stream capture). */
 int bsmr_plan_reserve(bsmr_plan *plan, uint32_t K);
 
+/* ---- Alignment of device pointers ----
+ * Every device entry point below checks its pointers before any device work and returns BSMR_ERR_INVALID_ARG for one
+ * below the alignment its argument needs (a NULL that the call allows counts as aligned):
+ *   16 bytes  the operand matrices and their 16-bit copies: A_dev, B_dev (fp32, bsmr_sddmm, _batch, _timed, _lowp,
+ *             bsmr_plan_tune, bsmr_convert_operands, bsmr_sddmm_backward), A16_dev, B16_dev (bsmr_convert_operands,
+ *             bsmr_sddmm_lowp), X_dev, Y_dev (bsmr_spmm), dA_dev, dB_dev (bsmr_sddmm_backward).  The kernels move them 16
+ *             bytes at a time (global_load_dwordx4, LDS-DMA of 16 bytes per lane, 16-byte stores of the conversion pass,
+ *             float4 in the backward); K is a multiple of 32, so every row, column and batch then starts on 16 bytes.
+ *    4 bytes  the value arrays, read and written one float at a time: P_dev (all of the above), v_dev (bsmr_spmm),
+ *             dP_dev (bsmr_sddmm_backward), X_dev / Y_dev / dY_dev / dX_dev of bsmr_sparse_softmax[_backward], and
+ *             in_dev / out_dev of bsmr_batched_transpose.  A batch with an odd nnz puts its second problem on an odd
+ *             float; that is within the contract.
+ * No call reads or writes outside the extents its comment states (M K, N K, nnz elements, times num_batches), whatever
+ * lies around them (tests/test_gpu_memory_contract.py).  bsmr_sddmm_host takes host pointers: no requirement. */
+
 /* One SDDMM: A_dev is M x K row-major fp32, B_dev is K x N column-major fp32
  * (column j = K contiguous floats at B_dev + j*K), P_dev receives nnz floats in
  * S's CSR order.  Every element of P_dev is overwritten. */
@@ -508,7 +523,8 @@ int bsmr_sharded_sddmm_host(bsmr_sharded *s, uint32_t K, const float *A_host, co
  * P = (A B^T) at S's stored positions has the gradients dA = S_dP B and dB = S_dP^T A; attention follows an SDDMM with
  * Y = S_v X.  All are one gather-and-accumulate: for destination d with list L(d), Y[d,:] = sum_{t in L(d)} v[e(t)] X[s(t),:]
  * (transpose 0: the rows of S, e(t) = t, s(t) = col_indices[t]; transpose 1: the columns of S, e(t) = csc_to_csr[t],
- * s(t) = csc_rows[t]).  X and Y are row-major with K contiguous floats per row (the layout of A and B), 16-byte aligned.
+ * s(t) = csc_rows[t]).  X and Y are row-major with K contiguous floats per row (the layout of A and B), 16-byte aligned;
+ * v and dP need the 4 bytes of a float ("Alignment of device pointers" above).
  *
  * Numerical contract: each destination's sum runs in its list's order (CSR order for rows, ascending row for columns) as
  * a sequential fp32 fma chain; a list longer than BSMR_BACKWARD_CHUNK is summed chunk by chunk and the partials are added

@@ -64,6 +64,10 @@ def test_argument_validation_without_gpu(engine):
     assert hip.bsmr_memcpy_h2d(None, None, 8) == engine.ERR_INVALID_ARG
     assert hip.bsmr_sddmm_batch(None, 32, None, None, None, 2, 0, None) == engine.ERR_INVALID_ARG
     assert hip.bsmr_batched_transpose(4, 4, 1, None, None, None) == engine.ERR_INVALID_ARG
+    # a pointer below a float's alignment is refused before anything else (width 0: nothing would be launched anyway)
+    assert hip.bsmr_batched_transpose(0, 4, 1, 2, 8, None) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_batched_transpose(0, 4, 1, 8, 6, None) == engine.ERR_INVALID_ARG
+    assert hip.bsmr_batched_transpose(0, 4, 1, 8, 16, None) == engine.OK
     assert hip.bsmr_plan_sparse_choice(None, 32, 0, None, None) == engine.ERR_INVALID_ARG
     assert hip.bsmr_cluster_rows(0, 4, 4, None, None, 16, 0.3, None, None, None, None) == engine.ERR_INVALID_ARG
 
