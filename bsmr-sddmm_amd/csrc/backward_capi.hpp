@@ -25,8 +25,10 @@ struct bsmr_backward {
     bool permuteV = true;             // dB reads dP permuted into CSC order by a pass of its own (measured faster on 3 of
                                       // the 4 lab shapes); BSMR_BACKWARD_PERMUTE=0: through csc_to_csr in place
     uint64_t indexBytes = 0;
-    float* work = nullptr;            // chunk partials (+ permuted dP), grown on demand
-    uint64_t workFloats = 0;
+    int lanes16 = 0;                  // elements per lane of spmmGather16: 0 = the measured choice per slice width
+                                      // (DESIGN 11); BSMR_GATHER16_LANES=4 / 8 at create: that layout for every width
+    float* work = nullptr;            // chunk partials (+ permuted dP) (+ 16-bit copies of the gathered operands),
+    uint64_t workFloats = 0;          // grown on demand
 
     ~bsmr_backward() {
         for (void* p : {(void*)rowOffsets, (void*)colIndices, (void*)cscRows, (void*)cscToCsr, (void*)items[0], (void*)items[1],
@@ -94,6 +96,48 @@ uint64_t workFloatsFor(const bsmr_backward* bw, uint32_t K, uint32_t nb, bool wi
     return (slots * K + (withPermute ? bw->nnz : 0u)) * nb;
 }
 
+// The 16-bit copies of a *_mode call lie behind that call's partials and permuted values, on the next 16 bytes
+// (hipMalloc aligns the workspace itself); two 16-bit elements per float of the workspace.
+uint64_t lowpOffset(const bsmr_backward* bw, uint32_t K, uint32_t nb, bool withPermute) {
+    return (workFloatsFor(bw, K, nb, withPermute) + 3u) & ~3ull;
+}
+
+bool validMode(int mode) { return mode == BSMR_COMPUTE_F16 || mode == BSMR_COMPUTE_BF16 || mode == BSMR_COMPUTE_F32; }
+
+// fp32 -> fp16 / bf16, round to nearest even: the forward's own pass (convertOperands) in plain order over one or two
+// contiguous arrays of n0 / n1 elements (multiples of 32); one launch
+int roundOperands(int mode, const float* X0, uint64_t n0, uint16_t* O0, const float* X1, uint64_t n1, uint16_t* O1,
+                  hipStream_t s) {
+    const uint64_t n8 = (n0 + n1) / 8u;
+    if (n8 == 0) return BSMR_OK;
+    const dim3 grid((uint32_t)std::min<uint64_t>((n8 + bsmr::kThreads - 1) / bsmr::kThreads, 256u * 16u));
+    if (mode == BSMR_COMPUTE_F16)
+        hipLaunchKernelGGL(bsmr::convertOperands<0>, grid, dim3(bsmr::kThreads), 0, s, X0, n0 / 8u, X1, n1 / 8u, O0, O1, false);
+    else
+        hipLaunchKernelGGL(bsmr::convertOperands<1>, grid, dim3(bsmr::kThreads), 0, s, X0, n0 / 8u, X1, n1 / 8u, O0, O1, false);
+    BSMR_HIP(hipGetLastError());
+    return BSMR_OK;
+}
+
+// Elements per lane of spmmGather16 for slice width W: 8 (16-byte loads) or 4 (8-byte loads).  W = 256 and 128 (DESIGN
+// 11): 8 is up to 1.4x faster on the large shapes, 4 is 1.2x faster on the small nips-like one, where fp32 beats both.
+// W = 64 and 32 are not measured: they keep the fp32 kernel's groups of 16 / 8 lanes.
+uint32_t lanes16For(const bsmr_backward* bw, uint32_t W) {
+    if (bw->lanes16) return (uint32_t)bw->lanes16;
+    return W >= 128u ? 8u : 4u;
+}
+
+template <int W, int VE, typename... Args>
+void launchGather16(bool map, int mode, dim3 grid, hipStream_t s, Args... args) {
+    if (mode == BSMR_COMPUTE_F16) {
+        if (map) hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, true, 0>), grid, dim3(256), 0, s, args...);
+        else hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, false, 0>), grid, dim3(256), 0, s, args...);
+    } else {
+        if (map) hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, true, 1>), grid, dim3(256), 0, s, args...);
+        else hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, false, 1>), grid, dim3(256), 0, s, args...);
+    }
+}
+
 int growWork(bsmr_backward* bw, uint64_t floats) {
     if (floats <= bw->workFloats) return BSMR_OK;
     if (bw->work) BSMR_HIP(hipFree(bw->work));
@@ -112,8 +156,13 @@ int checkBackwardCall(const bsmr_backward* bw, uint32_t K, uint32_t nb) {
     return BSMR_OK;
 }
 
-// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.
-int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const float* X, float* Y, uint32_t nb, hipStream_t s) {
+// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.  xMode says what
+// the rows of X are: fp32 (spmmGather), or fp16 / bf16 (spmmGather16).
+int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* Xrows, float* Y, uint32_t nb, hipStream_t s,
+            int xMode = BSMR_COMPUTE_F32) {
+    const bool lowp = xMode != BSMR_COMPUTE_F32;
+    const float* X = lowp ? nullptr : static_cast<const float*>(Xrows);
+    const uint16_t* X16 = lowp ? static_cast<const uint16_t*>(Xrows) : nullptr;
     const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
     const uint64_t nnz = bw->nnz;
     const uint64_t xB = (uint64_t)rowsX * K, yB = (uint64_t)rowsY * K, pB = (uint64_t)bw->numSlots[dir] * K;
@@ -130,9 +179,26 @@ int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const float*
     const uint32_t W = K % 256u == 0 ? 256u : K % 128u == 0 ? 128u : K % 64u == 0 ? 64u : 32u;
     const uint32_t slices = K / W;
     const uint64_t units = (uint64_t)bw->numItems[dir] * slices;
-    const uint64_t unitsPerBlock = 4u * (W >= 128u ? 1u : 64u / (W / 4u));
+    const uint32_t VE = lowp ? lanes16For(bw, W) : 0u;
+    const uint64_t unitsPerBlock = lowp ? 4u * (64u / (W / VE)) : 4u * (W >= 128u ? 1u : 64u / (W / 4u));
     const dim3 grid((uint32_t)((units + unitsPerBlock - 1) / unitsPerBlock), nb);
-    if (units) {
+    if (units && lowp) {
+#define BSMR_SPMM16_LAUNCH(WW)                                                                                               \
+    if (VE == 8u)                                                                                                            \
+        launchGather16<WW, 8>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, Y, \
+                              partial, K, nnz, xB, yB, pB);                                                                  \
+    else                                                                                                                     \
+        launchGather16<WW, 4>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, Y, \
+                              partial, K, nnz, xB, yB, pB)
+        switch (W) {
+        case 256: BSMR_SPMM16_LAUNCH(256); break;
+        case 128: BSMR_SPMM16_LAUNCH(128); break;
+        case 64: BSMR_SPMM16_LAUNCH(64); break;
+        default: BSMR_SPMM16_LAUNCH(32); break;
+        }
+#undef BSMR_SPMM16_LAUNCH
+        BSMR_HIP(hipGetLastError());
+    } else if (units) {
 #define BSMR_SPMM_LAUNCH(WW, MAP)                                                                                            \
     hipLaunchKernelGGL((bsmr::spmmGather<WW, MAP>), grid, dim3(256), 0, s, bw->items[dir], bw->numItems[dir], slices, src, \
                        map, v, X, Y, partial, K, nnz, xB, yB, pB)
@@ -198,6 +264,9 @@ int bsmr_backward_create(bsmr_backward** out, int device, uint32_t M, uint32_t N
         bw->nnz = nnz;
         const char* perm = std::getenv("BSMR_BACKWARD_PERMUTE");
         bw->permuteV = !perm || std::atoi(perm) != 0;
+        const char* lanes = std::getenv("BSMR_GATHER16_LANES");
+        const int l16 = lanes ? std::atoi(lanes) : 0;
+        bw->lanes16 = l16 == 4 || l16 == 8 ? l16 : 0;
         std::vector<uint32_t> co(N + 1u), cscRows(nnz), cscToCsr(nnz), ci(col_indices, col_indices + nnz);
         csrTranspose(M, N, nnz, row_offsets, col_indices, co.data(), cscRows.data(), cscToCsr.data());
         std::vector<uint32_t> cols(N);
@@ -284,6 +353,78 @@ int bsmr_sddmm_backward(bsmr_backward* bw, uint32_t K, const float* dP_dev, cons
         if (int st = runSpmm(bw, K, 0, dP_dev, B_dev, dA_dev, num_batches, s)) return st;
     if (dB_dev)
         if (int st = runSpmm(bw, K, 1, dP_dev, A_dev, dB_dev, num_batches, s)) return st;
+    return BSMR_OK;
+}
+
+int bsmr_backward_reserve_mode(bsmr_backward* bw, uint32_t K, uint32_t num_batches, int compute_mode) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    if (!validMode(compute_mode)) return BSMR_ERR_INVALID_ARG;
+    if (compute_mode == BSMR_COMPUTE_F32) return bsmr_backward_reserve(bw, K, num_batches);
+    BSMR_HIP(hipSetDevice(bw->device));
+    // the largest covered call: bsmr_sddmm_backward_mode with both outputs (copies of A and of B)
+    const uint32_t nb = std::max(num_batches, 1u);
+    return growWork(bw, lowpOffset(bw, K, nb, bw->permuteV) + ((uint64_t)bw->M + bw->N) * K * nb / 2u);
+}
+
+int bsmr_spmm_mode(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, const float* X_dev, float* Y_dev,
+                   uint32_t num_batches, int compute_mode, void* stream) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    if (!validMode(compute_mode)) return BSMR_ERR_INVALID_ARG;
+    if (compute_mode == BSMR_COMPUTE_F32) return bsmr_spmm(bw, K, transpose, v_dev, X_dev, Y_dev, num_batches, stream);
+    if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
+    const bool reads = bw->nnz != 0;
+    if ((reads && (!v_dev || !X_dev)) || !Y_dev || !aligned4(v_dev) || !aligned16(X_dev) || !aligned16(Y_dev))
+        return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0) return BSMR_OK;
+    BSMR_HIP(hipSetDevice(bw->device));
+    const uint64_t n = reads ? (uint64_t)(transpose ? bw->M : bw->N) * K * num_batches : 0u;   // nnz = 0 reads no X
+    const uint64_t off = lowpOffset(bw, K, num_batches, bw->permuteV && transpose);
+    if (int st = growWork(bw, off + n / 2u)) return st;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    uint16_t* X16 = reinterpret_cast<uint16_t*>(bw->work + off);
+    if (int st = roundOperands(compute_mode, X_dev, n, X16, nullptr, 0, nullptr, s)) return st;
+    return runSpmm(bw, K, transpose, v_dev, X16, Y_dev, num_batches, s, compute_mode);
+}
+
+int bsmr_spmm_lowp(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, const void* X16_dev, float* Y_dev,
+                   uint32_t num_batches, int compute_mode, void* stream) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    if (compute_mode != BSMR_COMPUTE_F16 && compute_mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
+    if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
+    const bool reads = bw->nnz != 0;
+    if ((reads && (!v_dev || !X16_dev)) || !Y_dev || !aligned4(v_dev) || !aligned16(X16_dev) || !aligned16(Y_dev))
+        return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0) return BSMR_OK;
+    BSMR_HIP(hipSetDevice(bw->device));
+    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
+    return runSpmm(bw, K, transpose, v_dev, X16_dev, Y_dev, num_batches, static_cast<hipStream_t>(stream), compute_mode);
+}
+
+int bsmr_sddmm_backward_mode(bsmr_backward* bw, uint32_t K, const float* dP_dev, const float* A_dev, const float* B_dev,
+                             float* dA_dev, float* dB_dev, uint32_t num_batches, int compute_mode, void* stream) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    if (!validMode(compute_mode)) return BSMR_ERR_INVALID_ARG;
+    if (compute_mode == BSMR_COMPUTE_F32)
+        return bsmr_sddmm_backward(bw, K, dP_dev, A_dev, B_dev, dA_dev, dB_dev, num_batches, stream);
+    const bool reads = bw->nnz != 0;
+    if ((reads && !dP_dev) || !aligned4(dP_dev) || (dA_dev && ((reads && !B_dev) || !aligned16(B_dev) || !aligned16(dA_dev))) ||
+        (dB_dev && ((reads && !A_dev) || !aligned16(A_dev) || !aligned16(dB_dev))))
+        return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0 || (!dA_dev && !dB_dev)) return BSMR_OK;
+    BSMR_HIP(hipSetDevice(bw->device));
+    // B is gathered by dA, A by dB: only what a requested product reads is rounded, B16 first, A16 behind it
+    const uint64_t nB = reads && dA_dev ? (uint64_t)bw->N * K * num_batches : 0u;
+    const uint64_t nA = reads && dB_dev ? (uint64_t)bw->M * K * num_batches : 0u;
+    const uint64_t off = lowpOffset(bw, K, num_batches, bw->permuteV && dB_dev);
+    if (int st = growWork(bw, off + (nA + nB) / 2u)) return st;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    uint16_t* B16 = reinterpret_cast<uint16_t*>(bw->work + off);
+    uint16_t* A16 = B16 + nB;
+    if (int st = roundOperands(compute_mode, A_dev, nA, A16, B_dev, nB, B16, s)) return st;
+    if (dA_dev)
+        if (int st = runSpmm(bw, K, 0, dP_dev, B16, dA_dev, num_batches, s, compute_mode)) return st;
+    if (dB_dev)
+        if (int st = runSpmm(bw, K, 1, dP_dev, A16, dB_dev, num_batches, s, compute_mode)) return st;
     return BSMR_OK;
 }
 

@@ -15,10 +15,16 @@
 // An item of a split list writes its partial row to the workspace; spmmReduce then adds each destination's partials in
 // chunk order.  No atomics: every output element has exactly one writer, and its value does not depend on the schedule.
 // All row and output addresses are formed in 64 bits (N * K * 4 passes 4 GiB at reddit scale, batches multiply it).
+//
+// spmmGather16 is the same kernel over a 16-bit X (fp16 or bf16 rows, the copies convertOperands makes): half the
+// gathered bytes, every element widened to fp32 - exactly - before the same fma chain, so the result is the fp32 contract
+// on (v, round(X)) bit for bit, whichever lane holds which element.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "sddmm_kernels.hpp"   // u32x4; convertOperands (packLowp), the pass that rounds X
 
 namespace bsmr {
 
@@ -114,6 +120,102 @@ spmmGather(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSlic
     float* dst = item.slot == kBwDirect ? Y + b * yBatch + (uint64_t)item.dest * K
                                         : partial + b * pBatch + (uint64_t)item.slot * K;
     *reinterpret_cast<T*>(dst + (uint64_t)slice * W + (uint64_t)gl * V) = acc;
+}
+
+// The 16-bit words one lane loads (VE elements: 8 -> 16 bytes, 4 -> 8 bytes) and their exact widening to fp32.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <int VE> struct BwWords;
+template <> struct BwWords<4> { using T = u32x2; };
+template <> struct BwWords<8> { using T = u32x4; };
+
+// MODE 0: two fp16 (v_cvt_f32_f16 keeps fp16 subnormals, inf and NaN); MODE 1: two bf16 (the upper half of an fp32).
+// Element 2i is the low half of word i.
+template <int MODE>
+__device__ __forceinline__ void bwWiden(uint32_t pair, float& lo, float& hi) {
+    if constexpr (MODE == 0) {
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+        const f16x2 h = __builtin_bit_cast(f16x2, pair);
+        lo = (float)h[0];
+        hi = (float)h[1];
+    } else {
+        lo = __uint_as_float(pair << 16);
+        hi = __uint_as_float(pair & 0xFFFF0000u);
+    }
+}
+
+template <int MODE, int VE>
+__device__ __forceinline__ void bwFma16(float w, const typename BwWords<VE>::T& x, float (&acc)[VE]) {
+#pragma unroll
+    for (int i = 0; i < VE / 2; ++i) {
+        float lo, hi;
+        bwWiden<MODE>(x[i], lo, hi);
+        acc[2 * i] = fmaf(w, lo, acc[2 * i]);
+        acc[2 * i + 1] = fmaf(w, hi, acc[2 * i + 1]);
+    }
+}
+
+// spmmGather over 16-bit source rows.  W: slice width in elements, as spmmGather; VE: elements per lane (8 = 16-byte
+// loads, 4 = 8-byte loads), G = W / VE lanes per unit, 64 / G units per wave.  A lane's load starts VE * 2 bytes into a
+// slice that starts W * 2 bytes into a row of K * 2 bytes (K a multiple of W, X 16-byte aligned): naturally aligned, and
+// the G loads of a unit cover one slice of one row.  v, the accumulators, the partials and Y are fp32.
+template <int W, int VE, bool MAP, int MODE>
+__global__ void __launch_bounds__(256)
+spmmGather16(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSlices, const uint32_t* __restrict__ src,
+             const uint32_t* __restrict__ map, const float* __restrict__ v, const uint16_t* __restrict__ X,
+             float* __restrict__ Y, float* __restrict__ partial, uint32_t K, uint64_t vBatch, uint64_t xBatch,
+             uint64_t yBatch, uint64_t pBatch) {
+    constexpr int G = W / VE;
+    constexpr int UPW = 64 / G;   // units per wave
+    static_assert(G >= 4 && G <= 64 && (VE == 4 || VE == 8), "lane layout");
+    using T = typename BwWords<VE>::T;
+    const uint32_t lane = threadIdx.x & 63u, gl = lane % G, groupBase = lane - gl;
+    const uint64_t unit = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * UPW + lane / G;
+    if (unit >= (uint64_t)numItems * numSlices) return;   // whole groups leave; a group only reads its own lanes
+    const uint32_t it = (uint32_t)(unit / numSlices), slice = (uint32_t)(unit % numSlices);
+    const BwItem item = items[it];
+    const uint64_t b = blockIdx.y;
+    const uint16_t* xs = X + b * xBatch + (uint64_t)slice * W + (uint64_t)gl * VE;
+    const float* vb = v + b * vBatch;
+    float acc[VE];
+#pragma unroll
+    for (int i = 0; i < VE; ++i) acc[i] = 0.f;
+    for (uint32_t t0 = item.begin; t0 < item.end; t0 += G) {
+        const uint32_t n = min((uint32_t)G, item.end - t0);
+        uint32_t s = 0, w = 0;
+        if (gl < n) {
+            const uint32_t t = t0 + gl;
+            s = src[t];
+            w = __float_as_uint(vb[MAP ? map[t] : t]);
+        }
+        uint32_t j = 0;
+        for (; j + 4 <= n; j += 4) {
+            const uint32_t s0 = bwBroadcast<G>(s, groupBase, j), s1 = bwBroadcast<G>(s, groupBase, j + 1);
+            const uint32_t s2 = bwBroadcast<G>(s, groupBase, j + 2), s3 = bwBroadcast<G>(s, groupBase, j + 3);
+            const float w0 = __uint_as_float(bwBroadcast<G>(w, groupBase, j));
+            const float w1 = __uint_as_float(bwBroadcast<G>(w, groupBase, j + 1));
+            const float w2 = __uint_as_float(bwBroadcast<G>(w, groupBase, j + 2));
+            const float w3 = __uint_as_float(bwBroadcast<G>(w, groupBase, j + 3));
+            const T x0 = *reinterpret_cast<const T*>(xs + (uint64_t)s0 * K);
+            const T x1 = *reinterpret_cast<const T*>(xs + (uint64_t)s1 * K);
+            const T x2 = *reinterpret_cast<const T*>(xs + (uint64_t)s2 * K);
+            const T x3 = *reinterpret_cast<const T*>(xs + (uint64_t)s3 * K);
+            bwFma16<MODE, VE>(w0, x0, acc);
+            bwFma16<MODE, VE>(w1, x1, acc);
+            bwFma16<MODE, VE>(w2, x2, acc);
+            bwFma16<MODE, VE>(w3, x3, acc);
+        }
+        for (; j < n; ++j) {
+            const uint32_t sj = bwBroadcast<G>(s, groupBase, j);
+            const float wj = __uint_as_float(bwBroadcast<G>(w, groupBase, j));
+            bwFma16<MODE, VE>(wj, *reinterpret_cast<const T*>(xs + (uint64_t)sj * K), acc);
+        }
+    }
+    float* dst = (item.slot == kBwDirect ? Y + b * yBatch + (uint64_t)item.dest * K
+                                         : partial + b * pBatch + (uint64_t)item.slot * K) +
+                 (uint64_t)slice * W + (uint64_t)gl * VE;
+#pragma unroll
+    for (int i = 0; i < VE; i += 4)
+        *reinterpret_cast<float4*>(dst + i) = make_float4(acc[i], acc[i + 1], acc[i + 2], acc[i + 3]);
 }
 
 // Y[dest] = partial[firstSlot] + partial[firstSlot + 1] + ... in chunk order; one thread per 4 floats of a split row.

@@ -208,6 +208,13 @@ HIP_SYMBOLS = {
     "bsmr_spmm": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsmr_sddmm_backward": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint32, C.c_void_p]),
+    "bsmr_backward_reserve_mode": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),
+    "bsmr_spmm_mode": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                 C.c_void_p]),
+    "bsmr_sddmm_backward_mode": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_spmm_lowp": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                 C.c_void_p]),
     "bsmr_sparse_softmax": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsmr_sparse_softmax_backward": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                C.c_void_p]),
@@ -705,8 +712,12 @@ def backward_destroy(bw):
     hip().bsmr_backward_destroy(bw)
 
 
-def backward_reserve(bw, K: int, num_batches: int = 1):
-    _check(hip().bsmr_backward_reserve(bw, K, num_batches), "bsmr_backward_reserve")
+def backward_reserve(bw, K: int, num_batches: int = 1, mode=COMPUTE_F32):
+    """workspace for calls with (K, num_batches, mode); mode F16 / BF16 adds room for the 16-bit copies"""
+    if mode == COMPUTE_F32:
+        _check(hip().bsmr_backward_reserve(bw, K, num_batches), "bsmr_backward_reserve")
+    else:
+        _check(hip().bsmr_backward_reserve_mode(bw, K, num_batches, mode), "bsmr_backward_reserve_mode")
 
 
 def backward_stats(bw) -> dict:
@@ -715,15 +726,33 @@ def backward_stats(bw) -> dict:
     return {k: getattr(s, k) for k, _ in BackwardStats._fields_}
 
 
-def spmm(bw, K: int, transpose: bool, v_ptr: int, X_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0):
-    """Y = S_v X (transpose False) or S_v^T X (True)"""
-    _check(hip().bsmr_spmm(bw, K, int(bool(transpose)), v_ptr, X_ptr, Y_ptr, num_batches, stream), "bsmr_spmm")
+def spmm(bw, K: int, transpose: bool, v_ptr: int, X_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0,
+         mode=COMPUTE_F32):
+    """Y = S_v X (transpose False) or S_v^T X (True); mode F16 / BF16: X is rounded and gathered as 16-bit rows"""
+    if mode == COMPUTE_F32:
+        _check(hip().bsmr_spmm(bw, K, int(bool(transpose)), v_ptr, X_ptr, Y_ptr, num_batches, stream), "bsmr_spmm")
+    else:
+        _check(hip().bsmr_spmm_mode(bw, K, int(bool(transpose)), v_ptr, X_ptr, Y_ptr, num_batches, mode, stream),
+               "bsmr_spmm_mode")
 
 
-def sddmm_backward(bw, K: int, dP_ptr: int, A_ptr: int, B_ptr: int, dA_ptr, dB_ptr, num_batches: int = 1, stream: int = 0):
-    """dA = S_dP B, dB = S_dP^T A; dA_ptr / dB_ptr None (or 0) skips that product"""
-    _check(hip().bsmr_sddmm_backward(bw, K, dP_ptr, A_ptr, B_ptr, dA_ptr or None, dB_ptr or None, num_batches, stream),
-           "bsmr_sddmm_backward")
+def spmm_lowp(bw, K: int, transpose: bool, v_ptr: int, X16_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0,
+              mode=COMPUTE_F16):
+    """spmm on rows the caller holds as fp16 (mode F16) or bf16 (BF16), e.g. an output of convert_operands"""
+    _check(hip().bsmr_spmm_lowp(bw, K, int(bool(transpose)), v_ptr, X16_ptr, Y_ptr, num_batches, mode, stream),
+           "bsmr_spmm_lowp")
+
+
+def sddmm_backward(bw, K: int, dP_ptr: int, A_ptr: int, B_ptr: int, dA_ptr, dB_ptr, num_batches: int = 1, stream: int = 0,
+                   mode=COMPUTE_F32):
+    """dA = S_dP B, dB = S_dP^T A; dA_ptr / dB_ptr None (or 0) skips that product; mode F16 / BF16: B (for dA) and A
+    (for dB) are rounded and gathered as 16-bit rows"""
+    if mode == COMPUTE_F32:
+        _check(hip().bsmr_sddmm_backward(bw, K, dP_ptr, A_ptr, B_ptr, dA_ptr or None, dB_ptr or None, num_batches, stream),
+               "bsmr_sddmm_backward")
+    else:
+        _check(hip().bsmr_sddmm_backward_mode(bw, K, dP_ptr, A_ptr, B_ptr, dA_ptr or None, dB_ptr or None, num_batches,
+                                              mode, stream), "bsmr_sddmm_backward_mode")
 
 
 def sparse_softmax(bw, scale: float, X_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0):

@@ -10,9 +10,18 @@ All are torch.autograd.Functions whose backward runs on the engine (bsmr_sddmm_b
 bsmr_sparse_softmax_backward), attention by composing the other three:
     sddmm:    dA = S_dP B,  dB = S_dP^T A    (exact fp32 products of the given operands in every mode: the forward's
                                               operand rounding is treated as straight-through)
+              with gather_mode = F16 / BF16:  dA = S_dP round(B),  dB = S_dP^T round(A) - the straight-through
+                                              gradients of the product of the ROUNDED operands, which is what the
+                                              forward computes when `mode` is the same format
     softmax:  dX = (W * (dW - rowsum(W * dW))) * scale   (bsmr_sparse_softmax_backward: bitwise reproducible)
     spmm:     d values = sddmm(dY, X)  (transposed: sddmm(X, dY)),  dX = spmm(values, dY, not transpose)
 so SDDMM -> softmax -> SpMM, the usual sparse-attention layer, trains on the engine end to end.
+
+gather_mode (default COMPUTE_F32: every result bit for bit as without the argument) is the format in which the gathers
+read their operand rows: with COMPUTE_F16 / COMPUTE_BF16 spmm's X, the dY of its dX, and the B / A of sddmm's dA / dB are
+rounded once per call and gathered as 16-bit rows (half the bytes); values, sums and results stay fp32.  spmm then
+returns S_values round(X), and its dX is S_values^T round(dY): the gradients of the rounded-operand products.  The
+SDDMM calls (the forward, d values of spmm) follow `mode`, not gather_mode.  Tensors are fp32 in either case.
 
 Every call runs on torch.cuda.current_stream(device).  Operands are fp32, contiguous, on the operator's device, with
 K a positive multiple of 32; anything else raises ValueError.  Double backward is not supported.  Calls on one operator
@@ -29,10 +38,13 @@ import bsmr_amd as eng
 
 
 class SparseOperator:
-    def __init__(self, csr: "eng.CSR", alpha=0.3, delta=0.3, mode=eng.COMPUTE_F16, device=0):
+    def __init__(self, csr: "eng.CSR", alpha=0.3, delta=0.3, mode=eng.COMPUTE_F16, device=0, gather_mode=eng.COMPUTE_F32):
+        if gather_mode not in (eng.COMPUTE_F16, eng.COMPUTE_BF16, eng.COMPUTE_F32):
+            raise ValueError(f"gather_mode: {gather_mode!r} is not one of COMPUTE_F16, COMPUTE_BF16, COMPUTE_F32")
         self.csr = csr
         self.M, self.N, self.nnz = csr.rows, csr.cols, csr.nnz
         self.mode = mode
+        self.gather_mode = gather_mode
         self.device = torch.device("cuda", device)
         self._plan = self._bw = None
         self.pipeline = eng.Pipeline(csr, alpha=alpha, delta=delta, device=-1)   # host arrays (RPHM) only
@@ -132,7 +144,8 @@ class SparseOperator:
         b, K = self._check(X, "X", rows_x, None)
         self._check_values(v, b)
         Y = torch.empty((rows_y, K) if b is None else (b, rows_y, K), dtype=torch.float32, device=self.device)
-        eng.spmm(self._bw, K, transpose, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream())
+        eng.spmm(self._bw, K, transpose, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
+                 mode=self.gather_mode)
         return Y
 
     def _softmax_args(self, v: torch.Tensor, scale):
@@ -170,7 +183,7 @@ class SparseOperator:
         dA = torch.empty_like(A) if need_a else None
         dB = torch.empty_like(B) if need_b else None
         eng.sddmm_backward(self._bw, K, dP.data_ptr(), A.data_ptr(), B.data_ptr(), dA.data_ptr() if need_a else None,
-                           dB.data_ptr() if need_b else None, b or 1, self._stream())
+                           dB.data_ptr() if need_b else None, b or 1, self._stream(), mode=self.gather_mode)
         return dA, dB
 
 

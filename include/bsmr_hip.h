@@ -36,6 +36,8 @@
  *   bsmr_csr_transpose   <- no reference counterpart: the host transpose bsmr_backward_create uploads
  *   bsmr_spmm / bsmr_sddmm_backward
  *                        <- no reference counterpart: Y = S_v X / S_v^T X and the two SDDMM gradients
+ *   bsmr_spmm_mode / bsmr_sddmm_backward_mode / bsmr_spmm_lowp / bsmr_backward_reserve_mode
+ *                        <- no reference counterpart: the same products with the gathered operand read as fp16 / bf16 rows
  *   bsmr_sparse_softmax / bsmr_sparse_softmax_backward
  *                        <- no reference counterpart: the row softmax over S's pattern and its gradient
  *   bsmr_mem_info        <- cudaMemGetInfo in calculateBlockSize (src/rowReordering.cu:1010-1013)
@@ -436,12 +438,13 @@ int bsmr_plan_reserve(bsmr_plan *plan, uint32_t K);
  * Every device entry point below checks its pointers before any device work and returns BSMR_ERR_INVALID_ARG for one
  * below the alignment its argument needs (a NULL that the call allows counts as aligned):
  *   16 bytes  the operand matrices and their 16-bit copies: A_dev, B_dev (fp32, bsmr_sddmm, _batch, _timed, _lowp,
- *             bsmr_plan_tune, bsmr_convert_operands, bsmr_sddmm_backward), A16_dev, B16_dev (bsmr_convert_operands,
- *             bsmr_sddmm_lowp), X_dev, Y_dev (bsmr_spmm), dA_dev, dB_dev (bsmr_sddmm_backward).  The kernels move them 16
- *             bytes at a time (global_load_dwordx4, LDS-DMA of 16 bytes per lane, 16-byte stores of the conversion pass,
- *             float4 in the backward); K is a multiple of 32, so every row, column and batch then starts on 16 bytes.
- *    4 bytes  the value arrays, read and written one float at a time: P_dev (all of the above), v_dev (bsmr_spmm),
- *             dP_dev (bsmr_sddmm_backward), X_dev / Y_dev / dY_dev / dX_dev of bsmr_sparse_softmax[_backward], and
+ *             bsmr_plan_tune, bsmr_convert_operands, bsmr_sddmm_backward[_mode]), A16_dev, B16_dev (bsmr_convert_operands,
+ *             bsmr_sddmm_lowp), X_dev, Y_dev (bsmr_spmm[_mode]), X16_dev, Y_dev (bsmr_spmm_lowp), dA_dev, dB_dev
+ *             (bsmr_sddmm_backward[_mode]).  The kernels move them 16 bytes at a time (global_load_dwordx4, LDS-DMA of 16
+ *             bytes per lane, 16-byte stores of the conversion pass, float4 and 8 x 16-bit loads in the backward); K is a
+ *             multiple of 32, so every row, column and batch then starts on 16 bytes.
+ *    4 bytes  the value arrays, read and written one float at a time: P_dev (all of the above), v_dev (bsmr_spmm[_mode],
+ *             bsmr_spmm_lowp), dP_dev (bsmr_sddmm_backward[_mode]), X_dev / Y_dev / dY_dev / dX_dev of bsmr_sparse_softmax[_backward], and
  *             in_dev / out_dev of bsmr_batched_transpose.  A batch with an odd nnz puts its second problem on an odd
  *             float; that is within the contract.
  * No call reads or writes outside the extents its comment states (M K, N K, nnz elements, times num_batches), whatever
@@ -544,7 +547,7 @@ typedef struct bsmr_backward_stats {
     uint32_t permute_values;      /* 1: the column direction permutes v into CSC order first (the default;
                                      BSMR_BACKWARD_PERMUTE=0 at create: read through csc_to_csr)  */
     uint64_t device_index_bytes;  /* index arrays resident on the device                          */
-    uint64_t workspace_bytes;     /* chunk partials (+ permuted values) reserved so far           */
+    uint64_t workspace_bytes;     /* chunk partials (+ permuted values, 16-bit copies) reserved so far */
 } bsmr_backward_stats;
 /* S as host CSR (row_offsets [M+1], col_indices [nnz]; read during the call only).  row_order: the order in which the
  * row destinations are scheduled (pass the pipeline's reordered_rows, the clustered order); it may list a subset, the
@@ -572,6 +575,38 @@ int bsmr_spmm(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, 
  * dP, A and B may be NULL; the requested outputs are still all zeros. */
 int bsmr_sddmm_backward(bsmr_backward *bw, uint32_t K, const float *dP_dev, const float *A_dev, const float *B_dev,
                         float *dA_dev, float *dB_dev, uint32_t num_batches, void *stream);
+
+/* ---- fp16 / bf16 gather modes of the two calls above (revision 5, added without any layout change) ----
+ * compute_mode = BSMR_COMPUTE_F32: exactly bsmr_spmm / bsmr_sddmm_backward / bsmr_backward_reserve - the same kernels,
+ * the same bits, the same workspace.  BSMR_COMPUTE_F16 / _BF16: the gathered operand - X for bsmr_spmm_mode, B for dA and
+ * A for dB - is read as 16-bit rows, half the gathered bytes; v / dP, the accumulation, the chunk partials and the outputs
+ * stay fp32.  bsmr_spmm_mode and bsmr_sddmm_backward_mode round the operand(s) once per call (round to nearest even, the
+ * casts of bsmr_convert_operands: fp16 subnormals kept, beyond the fp16 range +-inf, NaN stays NaN; one launch for A and
+ * B) into the handle's workspace, behind the chunk partials and the permuted values on the next 16 bytes; only what a
+ * requested product gathers is rounded.  bsmr_spmm_lowp takes rows the caller already holds in 16 bits (an output of
+ * bsmr_convert_operands, a half / bfloat16 buffer; 16-byte aligned, [b][rows][K]): no pass, no workspace for X;
+ * compute_mode says how to read them, BSMR_COMPUTE_F32 is BSMR_ERR_INVALID_ARG.
+ *
+ * Numerical contract: widening fp16 / bf16 to fp32 is exact, so the result is the fp32 contract of "SDDMM backward"
+ * applied to (v, round_mode(X)), bit for bit - the same chains, chunks and fma - with the same reproducibility: call to
+ * call, stream to stream, batch to batch, for any row_order, with or without BSMR_BACKWARD_PERMUTE, and whichever lane
+ * layout the 16-bit kernel runs in.  With x~ = round_mode(x):
+ *   |Y - S_v X| <= (n + 2) u sum|v||x~| + u16 sum|v||x|,  u = 2^-24, u16 = 2^-11 (fp16) or 2^-8 (bf16),
+ * for X inside the 16-bit format's normal range.  As gradients of an SDDMM that ran in the same mode these are the
+ * straight-through gradients of the function it computed: dA = S_dP round(B), dB = S_dP^T round(A).
+ *
+ * Arguments as the fp32 calls, checked before any device work: a NULL handle or a compute_mode outside {0, 1, 2} is
+ * BSMR_ERR_INVALID_ARG, K = 0 or not a multiple of 32 BSMR_ERR_UNSUPPORTED_K; the same alignments; with nnz = 0 v and X
+ * may be NULL and the outputs are all zeros; num_batches = 0 is a no-op, at most 65535 batches.  After
+ * bsmr_backward_reserve_mode(K, num_batches, compute_mode) every one of these calls with that (K, num_batches or fewer,
+ * mode) allocates nothing and can be captured in a graph. */
+int bsmr_backward_reserve_mode(bsmr_backward *bw, uint32_t K, uint32_t num_batches, int compute_mode);
+int bsmr_spmm_mode(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const float *X_dev, float *Y_dev,
+                   uint32_t num_batches, int compute_mode, void *stream);
+int bsmr_sddmm_backward_mode(bsmr_backward *bw, uint32_t K, const float *dP_dev, const float *A_dev, const float *B_dev,
+                             float *dA_dev, float *dB_dev, uint32_t num_batches, int compute_mode, void *stream);
+int bsmr_spmm_lowp(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const void *X16_dev, float *Y_dev,
+                   uint32_t num_batches, int compute_mode, void *stream);
 
 /* ---- Sparse row softmax (revision 5, added without any layout change; no reference counterpart) ----
  * The middle step of sparse attention (SDDMM -> softmax -> SpMM) on the same handle: values in S's CSR order, row r
