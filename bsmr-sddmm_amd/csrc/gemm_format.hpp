@@ -16,7 +16,10 @@
 //                             back and forth, so that every wave's entry lists are about equally long - the clustered
 //                             order puts heavy rows side by side (nips-like: 198 k entries in one row group, 44 k in
 //                             another; the fullest wave three times the mean).  Rows of A are gathered by id and a row's
-//                             entries are a run of P wherever the row sits, so the order is free (padding: row 0 of the list)
+//                             entries are a run of P wherever the row sits, so the order is free (padding: row 0 of the list).
+//                             Inside its half a row is placed so that the half's PASSES hold about equally many entries too
+//                             (greedy, packGemm 0a): the kernel's mask pass takes one trip of 256 / 512 words per list in
+//                             straight-line code and loops only for what is longer
 //   colOf     [S * TN]        the column of B in every column slot.  Slots follow the natural column order EXCEPT for hot
 //                             columns (more than twice the average number of dense entries), which are dealt over the S
 //                             strips by descending count (boustrophedon), so that no strip gathers them.  The MFMA work of a
@@ -66,6 +69,7 @@ constexpr uint32_t kGemmNoEntry = 0xFFFFFFFFu; // padding word (offset 8191 is n
 constexpr uint32_t kGemmMaxOffset = 8191u;
 constexpr uint32_t kGemmSlabStrips = 8;        // column strips per slab of the item order
 constexpr uint32_t kGemmWordSlack = 1024;      // words behind the last list that the kernel may read (never use)
+constexpr uint32_t kGemmMaxRowTiles = 8, kGemmMaxPasses = 3;   // of a wave, over the shapes of gemmShapeOk (m <= 8, m n <= 40)
 
 struct GemmItem {
     uint32_t group;        // row group: panels [group * PM, group * PM + PM)
@@ -130,9 +134,32 @@ inline int packGemm(const HostDense& hd, uint32_t PM, uint32_t NB, GemmFormatHos
         for (uint32_t i = 0; i < P * 16; ++i) order[i] = i;
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return weight[a] > weight[b]; });
         const uint32_t bins = 2 * G, half = TM / 2;
+        // ... and INSIDE a half over its passes.  Which half a row goes to fixes every wave's total; where it sits in the
+        // half decides which pass its entries fall into (tile tm * n + tn of a wave belongs to pass (tm * n + tn) / 16).
+        // Position = round number put the heaviest rows into the first row tiles, i.e. all into pass 0 (nips-like at
+        // 16 x 20: mean list of pass 0 / 1 / 2 257 / 115 / 27 words, a trip of the kernel is 256), and a launch ends with
+        // its longest pass.  Greedy: rows come by descending count; each goes to the row tile of its half with a free
+        // row that keeps the half's fullest pass smallest (the lowest such tile).  A row tile whose n columns lie in
+        // two passes (n = 5) weighs on each by its share: loads are kept in units of count x tiles, exact in integers.
+        uint32_t share[kGemmMaxRowTiles][kGemmMaxPasses] = {};
+        for (uint32_t tm = 0; tm < m; ++tm)
+            for (uint32_t tn = 0; tn < n; ++tn) ++share[tm][(tm * n + tn) / kGemmPassTiles];
+        std::vector<uint64_t> load((size_t)bins * Q, 0);
+        std::vector<uint8_t> rowsIn((size_t)bins * m, 0);
         for (uint32_t rank = 0; rank < P * 16; ++rank) {   // round `rank / bins` gives one row to every half
             const uint32_t round = rank / bins, pos = rank % bins, bin = (round & 1u) ? bins - 1u - pos : pos;
-            rowPos[order[rank]] = (bin / 2) * TM + (bin % 2) * half + round;
+            const uint64_t w = weight[order[rank]];
+            uint64_t* ld = &load[(size_t)bin * Q];
+            uint32_t best = m;
+            uint64_t bestFullest = 0;
+            for (uint32_t tm = 0; tm < m; ++tm) {
+                if (rowsIn[(size_t)bin * m + tm] == 16) continue;
+                uint64_t fullest = 0;
+                for (uint32_t q = 0; q < Q; ++q) fullest = std::max(fullest, ld[q] + w * share[tm][q]);
+                if (best == m || fullest < bestFullest) { best = tm; bestFullest = fullest; }
+            }
+            for (uint32_t q = 0; q < Q; ++q) ld[q] += w * share[best][q];
+            rowPos[order[rank]] = (bin / 2) * TM + (bin % 2) * half + best * 16u + rowsIn[(size_t)bin * m + best]++;
         }
     } else {
         for (uint32_t i = 0; i < P * 16; ++i) rowPos[i] = i;

@@ -25,8 +25,10 @@
 //     tiles: accumulators -> slab (ds_write_b128 per tile), then one lane per STORED entry: entry word -> slab value and the
 //     row's first index (a table of the macro-tile in LDS) -> one store.  The words of a (wave, pass) list are contiguous
 //     and ordered by (row, column): 64 lanes read 256 contiguous bytes and write runs of P.  Entry words are read once per
-//     launch, i.e. from HBM: the first eight batches of a pass are requested one phase ahead (pass 0's in front of the last
-//     slice's MFMAs).
+//     launch, i.e. from HBM: the first trip of a pass (four or eight batches of 64) is requested a pass or two ahead (pass
+//     0's with the first stage where the K loop is short, else in front of the last slice's MFMAs), and the passes are
+//     shaped so that the waits hipcc counts in front of a trip leave the younger requests and all stores outstanding
+//     (gemmMaskPass).
 //   * SRC32: the caller's fp32 operands, no conversion pass (K <= 128).  A stage then holds 32 k (rows of 128 bytes again:
 //     same DMA shape, K / 32 slices); a fragment is two ds_read_b128 (8 consecutive k as fp32) rounded in registers with the
 //     casts of convertOperands, so the MFMA operands - and P - are bit for bit those of conversion pass + 16-bit kernel.
@@ -130,22 +132,88 @@ __device__ __forceinline__ void gemmStagePart(const uint8_t* src, uint32_t srcBy
 // was a branch around a store: the compiler could not count the stores between a batch of entry words and its use any
 // more, waited with vmcnt(2), (1), (0) for words that had landed long before - and with them for the acknowledgements of
 // the stores issued in between (stores and loads share the counter on gfx9).
-#if !defined(BSMR_GEMM_BRANCHY_STORES)
 __device__ __forceinline__ void gemmStoreEntry(float* P, bool live, uint32_t index, float val) {
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(P, 0, 0xFFFFFFFC, 0x00020000);
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, val), rsrc, live ? index << 2 : 0xFFFFFFFFu, 0, 0);
 }
-#endif
+// ---- the mask pass, shared by denseGemm and denseGemmCvt
+// A TRIP is C batches of 64 entry words (C = 4 where the accumulators leave few registers, else 8).  Reads past a list stay
+// inside `words`: a trip is requested at most one trip past the end of a list, and kGemmWordSlack covers two trips of 512.
+template <uint32_t C>
+__device__ __forceinline__ void gemmLoadWords(const uint32_t* __restrict__ words, uint32_t e0, uint32_t lane, uint32_t (&w)[C], bool skip) {
+    // (e0 is wave-uniform: a scalar base, the lane's offset - one register for every request of the kernel - and an immediate)
+    const uint32_t* __restrict__ base = words + e0;
+#pragma unroll
+    for (uint32_t u = 0; u < C; ++u) w[u] = skip ? kGemmNoEntry : base[u * kWave + lane];
+}
+// One trip: the words of list positions e .. e + 64 C - 1 (the list ends at `last`), one lane per stored entry: slab value and
+// the row's first index -> one store.  Straight-line: the 2 C LDS reads go out together, the C stores back to back.  (A
+// padding word - and any word past the list - reads slot <= 4095 and row <= HALF - 1: inside the slab and the table.)
+template <uint32_t C, uint32_t HALF>
+__device__ __forceinline__ void gemmMaskTrip(const float* slab, const uint32_t* rowTable, float* P, uint32_t e, uint32_t last, uint32_t lane,
+                                             const uint32_t (&w)[C], bool skipStores) {
+#pragma unroll
+    for (uint32_t u = 0; u < C; ++u) {
+        const bool live = e + u * kWave + lane < last && w[u] != kGemmNoEntry;
+        const float val = slab[w[u] & 4095u];
+        const uint32_t dst = rowTable[(w[u] >> 12) & (HALF - 1u)] + (w[u] >> 19);
+        if (!skipStores) gemmStoreEntry(P, live, dst, val);
+    }
+}
+// Pass q of a wave over words[myList[q] .. myList[q + 1]).  Its first trip's words are in wAhead[q & 1], requested a pass or
+// more ago (DEEP: two passes ahead, where the registers allow it); the first trip of the pass that takes these registers
+// next is requested here, before anything of this pass is used.  What this shape is for is the waits hipcc counts in
+// front of the first trip.  Loads and stores share one in-order counter (vmcnt), so "the words have landed" can only be
+// said as "at most N younger operations are outstanding", and only where the compiler can count them:
+//   * the first trip is peeled out of the loop and issued unconditionally (an empty list issues C out-of-range stores).
+//     Inside `for (e = first; ...) { if (e != first) load(w); ... }` the registers of `w` were carried round the loop, the
+//     first trip's wait was merged with a later trip's - where `w` is the youngest load - and every pass began with
+//     vmcnt(0): a full round trip for the next pass's words requested four instructions earlier, and the drain of
+//     every store of the pass before;
+//   * a list longer than one trip requests its second trip BEFORE the first trip's first use, and the overflow loop requests
+//     trip t + 1 before it works on trip t, so that no trip's words are waited for behind the stores just issued.
+template <uint32_t C, uint32_t HALF, uint32_t Q, bool DEEP>
+__device__ __forceinline__ void gemmMaskPass(const uint32_t* __restrict__ words, const float* slab, const uint32_t* rowTable, float* P,
+                                             const uint32_t (&myList)[Q + 1u], uint32_t q, uint32_t lane, uint32_t (&wAhead)[2][C],
+                                             bool skipLoads, bool skipStores) {
+    const uint32_t first = myList[q], last = myList[q + 1u];
+    uint32_t w[C];
+#pragma unroll
+    for (uint32_t u = 0; u < C; ++u) w[u] = wAhead[q & 1u][u];
+    if (DEEP) {
+        if (q + 2u < Q) gemmLoadWords<C>(words, myList[q + 2u], lane, wAhead[q & 1u], skipLoads);
+    } else if (q + 1u < Q) {
+        gemmLoadWords<C>(words, last, lane, wAhead[(q + 1u) & 1u], skipLoads);   // (lists follow each other)
+    }
+    constexpr uint32_t T = C * kWave;
+    const bool more = first + T < last;   // (wave-uniform)
+    uint32_t over[C];
+    if (more) gemmLoadWords<C>(words, first + T, lane, over, skipLoads);
+    gemmMaskTrip<C, HALF>(slab, rowTable, P, first, last, lane, w, skipStores);
+    if (more) {
+        // (the request stands at the top of the body and its registers are copied at the bottom, with nothing conditional in
+        // between: written as two register sets and a body unrolled by two, hipcc sank each request below the loop's exit
+        // test, i.e. back to where the words are needed)
+        for (uint32_t e = first + T; e < last; e += T) {
+            uint32_t ahead[C];
+            gemmLoadWords<C>(words, e + T, lane, ahead, skipLoads);
+            gemmMaskTrip<C, HALF>(slab, rowTable, P, e, last, lane, over, skipStores);
+#pragma unroll
+            for (uint32_t u = 0; u < C; ++u) over[u] = ahead[u];
+        }
+    }
+}
 template <uint32_t ADMAS, uint32_t BDMAS>
 __device__ __forceinline__ void gemmStage(const uint8_t* A, uint32_t aBytes, const uint8_t* B, uint32_t bBytes, uint8_t* stage, uint32_t bAt,
                                           uint32_t wave, const uint32_t* voffA, const uint32_t* voffB, uint32_t kOff) {
     gemmStagePart<BDMAS>(B, bBytes, stage + bAt, wave, voffB, kOff);
     gemmStagePart<ADMAS>(A, aBytes, stage, wave, voffA, kOff);
 }
-// Row id of this lane's row in a chunk of 8 rows whose ids lie at `rows8` (a wave-uniform address): eight SCALAR loads and a
-// select.  A vector load here would sit in the same in-order counter as the LDS-DMAs issued before it, and hipcc waits for
-// everything (vmcnt(0)) at its first use: the first stage's B columns, which do not depend on the row ids, would have to land
-// before the A rows are even requested.  Scalar loads count on lgkmcnt.
+// Row id of this lane's row in a chunk of 8 rows whose ids lie at `rows8` (a wave-uniform address), written as eight loads of
+// uniform addresses and a select.  hipcc does not keep them scalar: it folds the select into the address and emits ONE
+// global_load_dword per chunk at rows8 + 4 sub (denseGemmCvt<4, 16, 20, 0>: nine, five for the B columns and four for the
+// A rows, all issued before the first DMA; each chunk's ids are then waited for with a counted vmcnt(8), (7), (7) ... in
+// front of its DMA, so no DMA waits for ids it does not need, and no id waits for a DMA).
 __device__ __forceinline__ uint32_t gemmRowOfLane(const uint32_t* __restrict__ rows8, uint32_t sub) {
     uint32_t id = rows8[0];
 #pragma unroll
@@ -235,37 +303,40 @@ denseGemm(const void* __restrict__ Aop, const void* __restrict__ Bop, uint32_t a
 #pragma unroll
         for (uint32_t j = 0; j < n; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // entry words, kGemmWordChunk batches of 64 at a time (reads past a list stay inside `words`: its slack)
-    auto loadWords = [&](uint32_t e0, uint32_t (&w)[kGemmWordChunk]) {
-#pragma unroll
-        for (uint32_t u = 0; u < kGemmWordChunk; ++u) w[u] = GEMM_LAB_SKIP(4) ? kGemmNoEntry : words[e0 + u * kWave + lane];
-    };
+    // entry words, a trip of kGemmWordChunk batches of 64 at a time
+    auto loadWords = [&](uint32_t e0, uint32_t (&w)[kGemmWordChunk]) { gemmLoadWords<kGemmWordChunk>(words, e0, lane, w, GEMM_LAB_SKIP(4)); };
     // the first words of the passes' lists are requested two passes ahead where the registers allow it (a pass is shorter
     // than the words' way from HBM: 0.1-0.2 us per launch at 256 x 256; the 8 x 5 tile blocks have no registers left for
     // it - 3 to 8 spilled, 0.25 us lost - and stay one pass ahead)
     constexpr bool kDeepWords = Q >= 2u && m * n <= 32u;
     uint32_t wAhead[2][kGemmWordChunk];
+    // pass 0's first entry words: an HBM round trip (they are read once per launch).  A short K loop does not cover it from
+    // the top of its last slice, so up to four slices request them before the loop and carry the registers through it - as
+    // soon as the list bounds are known: in front of the wait for the first stage, whose round trip they share.  (Requested
+    // behind the first barrier they stood right in front of slice 0's vmcnt(0), below which hipcc sinks that slice's
+    // MFMAs: the K loop waited for words the epilogue needs KT slices later.  BSMR_GEMM_LATE_WORDS: lab, that form.)
+    constexpr bool kEarlyWords = KT <= 4 && !kPlainDump;
+    auto firstWords = [&]() {
+        loadWords(myList[0], wAhead[0]);
+        if (kDeepWords) loadWords(myList[1], wAhead[1]);
+    };
+#if !defined(BSMR_GEMM_LATE_WORDS)
+    if (kEarlyWords) firstWords();
+#endif
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     GEMM_LAB_STAMP(2);
     __builtin_amdgcn_s_barrier();
     GEMM_LAB_STAMP(3);
-    // pass 0's first entry words: an HBM round trip (they are read once per launch).  A short K loop does not cover it from
-    // the top of its last slice, so up to four slices request them before the loop and carry the registers through it.
-    constexpr bool kEarlyWords = KT <= 4;
-    if (kEarlyWords) {
-        loadWords(myList[0], wAhead[0]);
-        if (kDeepWords) loadWords(myList[1], wAhead[1]);
-    }
+#if defined(BSMR_GEMM_LATE_WORDS)
+    if (kEarlyWords) firstWords();
+#endif
 
 #pragma unroll
     for (uint32_t t = 0; t < (uint32_t)KT; ++t) {
         if (t + 1u < (uint32_t)KT && !GEMM_LAB_SKIP(2))   // slice t + 1 -> the other stage
             gemmStage<ADMAS, BDMAS>(Ab, aBytes, Bb, bBytes, lds + ((t + 1u) & 1u) * stageBytes, bAt, wave, voffA, voffB, (t + 1u) * kGemmRowBytes);
-        if (!kEarlyWords && t + 1u == (uint32_t)KT) {   // ... a long loop: behind its last slice
-            loadWords(myList[0], wAhead[0]);
-            if (kDeepWords) loadWords(myList[1], wAhead[1]);
-        }
+        if (!kEarlyWords && t + 1u == (uint32_t)KT) firstWords();   // ... a long loop: behind its last slice's DMAs
         const uint8_t* base = lds + (t & 1u) * stageBytes;
 #pragma unroll
         for (uint32_t s = 0; s < KSUB; ++s) {
@@ -336,34 +407,11 @@ denseGemm(const void* __restrict__ Aop, const void* __restrict__ Bop, uint32_t a
                 }
             }
         }
-        const uint32_t first = myList[q], last = myList[q + 1u];
-        uint32_t w[kGemmWordChunk];
-#pragma unroll
-        for (uint32_t u = 0; u < kGemmWordChunk; ++u) w[u] = wAhead[q & 1u][u];
-        if (kDeepWords) {
-            if (q + 2u < Q) loadWords(myList[q + 2u], wAhead[q & 1u]);
-        } else if (q + 1u < Q) {
-            loadWords(last, wAhead[(q + 1u) & 1u]);                   // the next pass's first words (lists follow each other)
-        }
-        for (uint32_t e = first; e < last; e += kGemmWordChunk * kWave) {
-            if (e != first) loadWords(e, w);                         // (a list of more than 512 words: rare)
-#pragma unroll
-            for (uint32_t u = 0; u < kGemmWordChunk; ++u) {
-#if defined(BSMR_GEMM_BRANCHY_STORES)   // lab: the form with a branch per batch
-                if (e + u * kWave + lane < last && w[u] != kGemmNoEntry) {
-                    const float val = slab[w[u] & 4095u];
-                    const uint32_t dst = rowTable[(w[u] >> 12) & 127u] + (w[u] >> 19);
-                    if (!GEMM_LAB_SKIP(5)) P[dst] = val;
-                }
-#else
-                // (a padding word reads slot 4095 and row TM / 2 - 1: inside the slab and the table)
-                const bool live = e + u * kWave + lane < last && w[u] != kGemmNoEntry;
-                const float val = slab[w[u] & 4095u];
-                const uint32_t dst = rowTable[(w[u] >> 12) & (TM / 2u - 1u)] + (w[u] >> 19);
-                if (!GEMM_LAB_SKIP(5)) gemmStoreEntry(P, live, dst, val);
-#endif
-            }
-        }
+        // (the plain dump is ordinary code: without a fence hipcc's scheduler moves the pass's requests and LDS reads up
+        // between its stores, and the longer live ranges cost these 8 x 5 tile blocks 12 to 28 bytes of scratch at KT = 2 / 4 -
+        // whose reloads count on vmcnt and were waited for with vmcnt(0) in front of the first trip)
+        if (kPlainDump) __builtin_amdgcn_sched_barrier(0);
+        gemmMaskPass<kGemmWordChunk, TM / 2u, Q, kDeepWords>(words, slab, rowTable, P, myList, q, lane, wAhead, GEMM_LAB_SKIP(4), GEMM_LAB_SKIP(5));
         GEMM_LAB_STAMP(5u + q);
     }
     GEMM_LAB_STAMPS_OUT;
@@ -513,15 +561,18 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
     for (uint32_t i = 0; i < m; ++i)
 #pragma unroll
         for (uint32_t j = 0; j < n; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto loadWords = [&](uint32_t e0, uint32_t (&w)[kGemmWordChunk]) {
-#pragma unroll
-        for (uint32_t u = 0; u < kGemmWordChunk; ++u) w[u] = GEMM_LAB_SKIP(4) ? kGemmNoEntry : words[e0 + u * kWave + lane];
-    };
-    // the first words of the passes' lists are requested two passes ahead where the registers allow it (a pass is shorter
-    // than the words' way from HBM: 0.1-0.2 us per launch at 256 x 256; the 8 x 5 tile blocks have no registers left for
-    // it - 3 to 8 spilled, 0.25 us lost - and stay one pass ahead)
+    // entry words as in denseGemm: pass 0's first trip rides along with the first stage's round trip where the loop is short
+    auto loadWords = [&](uint32_t e0, uint32_t (&w)[kGemmWordChunk]) { gemmLoadWords<kGemmWordChunk>(words, e0, lane, w, GEMM_LAB_SKIP(4)); };
     constexpr bool kDeepWords = Q >= 2u && m * n <= 32u;
     uint32_t wAhead[2][kGemmWordChunk];
+    constexpr bool kEarlyWords = KT <= 4;
+    auto firstWords = [&]() {
+        loadWords(myList[0], wAhead[0]);
+        if (kDeepWords) loadWords(myList[1], wAhead[1]);
+    };
+#if !defined(BSMR_GEMM_LATE_WORDS)
+    if (kEarlyWords) firstWords();
+#endif
 
     // slice 0: landed (my chunks), rounded into H[0], slice 1 requested, H[0] published
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -531,19 +582,13 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
     if (KT > 1 && !GEMM_LAB_SKIP(2)) gemmStage<ADMAS, BDMAS>(Ab, aBytes, Bb, bBytes, lds, bAtF, wave, voffA, voffB, kGemmRowBytes);
     __builtin_amdgcn_s_barrier();
     GEMM_LAB_STAMP(3);
-    // pass 0's first entry words (an HBM round trip): a loop of up to four slices requests them here and carries them through
-    constexpr bool kEarlyWords = KT <= 4;
-    if (kEarlyWords) {
-        loadWords(myList[0], wAhead[0]);
-        if (kDeepWords) loadWords(myList[1], wAhead[1]);
-    }
+#if defined(BSMR_GEMM_LATE_WORDS)
+    if (kEarlyWords) firstWords();
+#endif
 
 #pragma unroll
     for (uint32_t t = 0; t < (uint32_t)KT; ++t) {
-        if (!kEarlyWords && t + 1u == (uint32_t)KT) {
-            loadWords(myList[0], wAhead[0]);
-            if (kDeepWords) loadWords(myList[1], wAhead[1]);
-        }
+        if (!kEarlyWords && t + 1u == (uint32_t)KT) firstWords();
         const uint8_t* base = lds + hAt + (t & 1u) * hBytes;
         u32x4 bf[n];
 #pragma unroll
@@ -596,34 +641,7 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
                 }
             }
         }
-        const uint32_t first = myList[q], last = myList[q + 1u];
-        uint32_t w[kGemmWordChunk];
-#pragma unroll
-        for (uint32_t u = 0; u < kGemmWordChunk; ++u) w[u] = wAhead[q & 1u][u];
-        if (kDeepWords) {
-            if (q + 2u < Q) loadWords(myList[q + 2u], wAhead[q & 1u]);
-        } else if (q + 1u < Q) {
-            loadWords(last, wAhead[(q + 1u) & 1u]);
-        }
-        for (uint32_t e = first; e < last; e += kGemmWordChunk * kWave) {
-            if (e != first) loadWords(e, w);
-#pragma unroll
-            for (uint32_t u = 0; u < kGemmWordChunk; ++u) {
-#if defined(BSMR_GEMM_BRANCHY_STORES)   // lab: the form with a branch per batch
-                if (e + u * kWave + lane < last && w[u] != kGemmNoEntry) {
-                    const float val = slab[w[u] & 4095u];
-                    const uint32_t dst = rowTable[(w[u] >> 12) & 127u] + (w[u] >> 19);
-                    if (!GEMM_LAB_SKIP(5)) P[dst] = val;
-                }
-#else
-                // (a padding word reads slot 4095 and row TM / 2 - 1: inside the slab and the table)
-                const bool live = e + u * kWave + lane < last && w[u] != kGemmNoEntry;
-                const float val = slab[w[u] & 4095u];
-                const uint32_t dst = rowTable[(w[u] >> 12) & (TM / 2u - 1u)] + (w[u] >> 19);
-                if (!GEMM_LAB_SKIP(5)) gemmStoreEntry(P, live, dst, val);
-#endif
-            }
-        }
+        gemmMaskPass<kGemmWordChunk, TM / 2u, Q, kDeepWords>(words, slab, rowTable, P, myList, q, lane, wAhead, GEMM_LAB_SKIP(4), GEMM_LAB_SKIP(5));
         GEMM_LAB_STAMP(5u + q);
     }
     GEMM_LAB_STAMPS_OUT;
