@@ -138,6 +138,18 @@ void launchGather16(bool map, int mode, dim3 grid, hipStream_t s, Args... args) 
     }
 }
 
+// ... with the finished rows stored in the format of X (bsmr_spmm_16, bsmr_sddmm_backward_16)
+template <int W, int VE, typename... Args>
+void launchGather16Out(bool map, int mode, dim3 grid, hipStream_t s, Args... args) {
+    if (mode == BSMR_COMPUTE_F16) {
+        if (map) hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, true, 0, uint16_t>), grid, dim3(256), 0, s, args...);
+        else hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, false, 0, uint16_t>), grid, dim3(256), 0, s, args...);
+    } else {
+        if (map) hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, true, 1, uint16_t>), grid, dim3(256), 0, s, args...);
+        else hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, false, 1, uint16_t>), grid, dim3(256), 0, s, args...);
+    }
+}
+
 int growWork(bsmr_backward* bw, uint64_t floats) {
     if (floats <= bw->workFloats) return BSMR_OK;
     if (bw->work) BSMR_HIP(hipFree(bw->work));
@@ -157,10 +169,13 @@ int checkBackwardCall(const bsmr_backward* bw, uint32_t K, uint32_t nb) {
 }
 
 // Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.  xMode says what
-// the rows of X are: fp32 (spmmGather), or fp16 / bf16 (spmmGather16).
-int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* Xrows, float* Y, uint32_t nb, hipStream_t s,
-            int xMode = BSMR_COMPUTE_F32) {
+// the rows of X are: fp32 (spmmGather), or fp16 / bf16 (spmmGather16).  y16 (16-bit X only): Yout holds xMode's format
+// too; otherwise fp32.
+int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* Xrows, void* Yout, uint32_t nb, hipStream_t s,
+            int xMode = BSMR_COMPUTE_F32, bool y16 = false) {
     const bool lowp = xMode != BSMR_COMPUTE_F32;
+    float* Y = y16 ? nullptr : static_cast<float*>(Yout);
+    uint16_t* Y16 = y16 ? static_cast<uint16_t*>(Yout) : nullptr;
     const float* X = lowp ? nullptr : static_cast<const float*>(Xrows);
     const uint16_t* X16 = lowp ? static_cast<const uint16_t*>(Xrows) : nullptr;
     const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
@@ -182,7 +197,23 @@ int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* 
     const uint32_t VE = lowp ? lanes16For(bw, W) : 0u;
     const uint64_t unitsPerBlock = lowp ? 4u * (64u / (W / VE)) : 4u * (W >= 128u ? 1u : 64u / (W / 4u));
     const dim3 grid((uint32_t)((units + unitsPerBlock - 1) / unitsPerBlock), nb);
-    if (units && lowp) {
+    if (units && y16) {
+#define BSMR_SPMM16_OUT_LAUNCH(WW)                                                                                           \
+    if (VE == 8u)                                                                                                            \
+        launchGather16Out<WW, 8>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, \
+                                 Y16, partial, K, nnz, xB, yB, pB);                                                          \
+    else                                                                                                                     \
+        launchGather16Out<WW, 4>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, \
+                                 Y16, partial, K, nnz, xB, yB, pB)
+        switch (W) {
+        case 256: BSMR_SPMM16_OUT_LAUNCH(256); break;
+        case 128: BSMR_SPMM16_OUT_LAUNCH(128); break;
+        case 64: BSMR_SPMM16_OUT_LAUNCH(64); break;
+        default: BSMR_SPMM16_OUT_LAUNCH(32); break;
+        }
+#undef BSMR_SPMM16_OUT_LAUNCH
+        BSMR_HIP(hipGetLastError());
+    } else if (units && lowp) {
 #define BSMR_SPMM16_LAUNCH(WW)                                                                                               \
     if (VE == 8u)                                                                                                            \
         launchGather16<WW, 8>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, Y, \
@@ -212,7 +243,15 @@ int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* 
 #undef BSMR_SPMM_LAUNCH
         BSMR_HIP(hipGetLastError());
     }
-    if (bw->numSplits[dir]) {
+    if (bw->numSplits[dir] && y16) {
+        const uint64_t threads = (uint64_t)bw->numSplits[dir] * (K / 4u);
+        const dim3 rgrid((uint32_t)((threads + 255u) / 256u), nb);
+        if (xMode == BSMR_COMPUTE_F16)
+            hipLaunchKernelGGL(bsmr::spmmReduce16<0>, rgrid, dim3(256), 0, s, bw->splits[dir], bw->numSplits[dir], partial, Y16, K, yB, pB);
+        else
+            hipLaunchKernelGGL(bsmr::spmmReduce16<1>, rgrid, dim3(256), 0, s, bw->splits[dir], bw->numSplits[dir], partial, Y16, K, yB, pB);
+        BSMR_HIP(hipGetLastError());
+    } else if (bw->numSplits[dir]) {
         const uint64_t threads = (uint64_t)bw->numSplits[dir] * (K / 4u);
         hipLaunchKernelGGL(bsmr::spmmReduce, dim3((uint32_t)((threads + 255u) / 256u), nb), dim3(256), 0, s, bw->splits[dir],
                            bw->numSplits[dir], partial, Y, K, yB, pB);
@@ -398,6 +437,40 @@ int bsmr_spmm_lowp(bsmr_backward* bw, uint32_t K, int transpose, const float* v_
     BSMR_HIP(hipSetDevice(bw->device));
     if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
     return runSpmm(bw, K, transpose, v_dev, X16_dev, Y_dev, num_batches, static_cast<hipStream_t>(stream), compute_mode);
+}
+
+int bsmr_spmm_16(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, const void* X16_dev, void* Y16_dev,
+                 uint32_t num_batches, int compute_mode, void* stream) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    if (compute_mode != BSMR_COMPUTE_F16 && compute_mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
+    if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
+    const bool reads = bw->nnz != 0;
+    if ((reads && (!v_dev || !X16_dev)) || !Y16_dev || !aligned4(v_dev) || !aligned16(X16_dev) || !aligned16(Y16_dev))
+        return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0) return BSMR_OK;
+    BSMR_HIP(hipSetDevice(bw->device));
+    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
+    return runSpmm(bw, K, transpose, v_dev, X16_dev, Y16_dev, num_batches, static_cast<hipStream_t>(stream), compute_mode, true);
+}
+
+int bsmr_sddmm_backward_16(bsmr_backward* bw, uint32_t K, const float* dP_dev, const void* A16_dev, const void* B16_dev,
+                           void* dA16_dev, void* dB16_dev, uint32_t num_batches, int compute_mode, void* stream) {
+    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
+    if (compute_mode != BSMR_COMPUTE_F16 && compute_mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
+    const bool reads = bw->nnz != 0;
+    if ((reads && !dP_dev) || !aligned4(dP_dev) ||
+        (dA16_dev && ((reads && !B16_dev) || !aligned16(B16_dev) || !aligned16(dA16_dev))) ||
+        (dB16_dev && ((reads && !A16_dev) || !aligned16(A16_dev) || !aligned16(dB16_dev))))
+        return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0 || (!dA16_dev && !dB16_dev)) return BSMR_OK;
+    BSMR_HIP(hipSetDevice(bw->device));
+    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && dB16_dev))) return st;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dA16_dev)
+        if (int st = runSpmm(bw, K, 0, dP_dev, B16_dev, dA16_dev, num_batches, s, compute_mode, true)) return st;
+    if (dB16_dev)
+        if (int st = runSpmm(bw, K, 1, dP_dev, A16_dev, dB16_dev, num_batches, s, compute_mode, true)) return st;
+    return BSMR_OK;
 }
 
 int bsmr_sddmm_backward_mode(bsmr_backward* bw, uint32_t K, const float* dP_dev, const float* A_dev, const float* B_dev,

@@ -2827,6 +2827,50 @@ int bsmr_sddmm_lowp(bsmr_plan* plan, uint32_t K, const void* A16, const void* B1
     return launchSparse(plan, K, A, B, P, s);
 }
 
+// The forward on 16-bit operands alone: every engine's 16-bit kernel (launchDense16) and the 16-bit residue kernel
+// (launchSparse16), whatever the plan says about the road its fp32 operands take.  Both read formats that do not
+// depend on that road: the GEMM and sweep formats are keyed by their shape alone (the fp32-operand GEMM kernels are
+// built for a subset of the 16-bit kernels' shapes) and size their LDS per launch from the operand type; a plan that
+// rounds in the streaming kernel keeps the streaming format launchStream reads; the tiles engine is only prepared
+// (prepareDense) where launchDense16 selects it; the residue lists are the same for both of its kernels.
+int bsmr_sddmm_16(bsmr_plan* plan, uint32_t K, const void* A16, const void* B16, float* P, uint32_t num_batches, int mode,
+                  void* stream) {
+    if (!plan) return BSMR_ERR_INVALID_ARG;
+    if (K == 0 || (K & 31u)) return BSMR_ERR_UNSUPPORTED_K;
+    if (mode != BSMR_COMPUTE_F16 && mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
+    plan = servedFor(plan, K, mode);
+    const bool reads = plan->nnz != 0;   // nnz = 0: nothing is read or written
+    if ((reads && (!A16 || !B16 || !P)) || !aligned16(A16) || !aligned16(B16) || !aligned4(P)) return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0 || !reads) return BSMR_OK;
+    if (num_batches > 65535u || (uint64_t)K * num_batches > 0xFFFFFFFFull) return BSMR_ERR_INVALID_ARG;
+    BSMR_HIP(hipSetDevice(plan->device));
+    const Queue s(static_cast<hipStream_t>(stream), bsmr::Batch{(uint64_t)plan->M * K, (uint64_t)plan->N * K, plan->nnz, num_batches});
+    if (int st = prepareDense(plan, K, mode)) return st;
+    const uint16_t* a = static_cast<const uint16_t*>(A16);
+    const uint16_t* b = static_cast<const uint16_t*>(B16);
+    const bool f16 = mode == BSMR_COMPUTE_F16;
+    auto runDense = [&](const Queue& q) -> int {
+        return f16 ? launchDense16<0>(plan, K, a, b, P, q) : launchDense16<1>(plan, K, a, b, P, q);
+    };
+    auto runSparse = [&](const Queue& q) -> int {
+        return f16 ? launchSparse16<0>(plan, K, a, b, P, q) : launchSparse16<1>(plan, K, a, b, P, q);
+    };
+    const bool hasDense = plan->fmt[0].numItems != 0 || plan->hostDense.entries() != 0;
+    const bool overlap = plan->sideStream && (plan->overlapNow >= 0 ? plan->overlapNow == 1 : plan->overlap);
+    int st = BSMR_OK;
+    if (overlap && hasDense && plan->numSparseItems) {   // the fork / join of runPieces
+        BSMR_HIP(hipEventRecord(plan->forkEvent, s));
+        BSMR_HIP(hipStreamWaitEvent(plan->sideStream, plan->forkEvent, 0));
+        if ((st = runSparse(Queue(plan->sideStream, s.batch))) != BSMR_OK) return st;
+        BSMR_HIP(hipEventRecord(plan->joinEvent, plan->sideStream));
+        if ((st = runDense(s)) != BSMR_OK) return st;
+        BSMR_HIP(hipStreamWaitEvent(s, plan->joinEvent, 0));
+        return BSMR_OK;
+    }
+    if (hasDense && (st = runDense(s)) != BSMR_OK) return st;
+    return runSparse(s);
+}
+
 int bsmr_sddmm_timed(bsmr_plan* plan, uint32_t K, const float* A, const float* B, float* P, int mode,
                      void* stream, int warmup, int iters, bsmr_timing* out) {
     plan = servedFor(plan, K, mode);

@@ -19,6 +19,11 @@
 // spmmGather16 is the same kernel over a 16-bit X (fp16 or bf16 rows, the copies convertOperands makes): half the
 // gathered bytes, every element widened to fp32 - exactly - before the same fma chain, so the result is the fp32 contract
 // on (v, round(X)) bit for bit, whichever lane holds which element.
+//
+// 16-bit outputs (bsmr_spmm_16, bsmr_sddmm_backward_16): spmmGather16 with YT = uint16_t and spmmReduce16 are the same
+// gather and the same reduction; only the one store of a finished destination row differs - it rounds the fp32 sums to
+// the format of X (bwNarrow: the casts of packLowp) and writes 2 bytes per element.  Chunk partials stay fp32 in the
+// workspace, so every output element is rounded exactly once.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -154,15 +159,36 @@ __device__ __forceinline__ void bwFma16(float w, const typename BwWords<VE>::T& 
     }
 }
 
+// Two fp32 sums rounded to MODE's format (round to nearest even, fp16 subnormals kept, +-inf beyond the range, NaN stays
+// NaN: the casts of packLowp), element 2i in the low half of word i - the inverse of bwWiden.
+template <int MODE>
+__device__ __forceinline__ uint32_t bwNarrow(float lo, float hi) {
+    if constexpr (MODE == 0) {
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+        f16x2 o;
+        o[0] = (_Float16)lo;
+        o[1] = (_Float16)hi;
+        return __builtin_bit_cast(uint32_t, o);
+    } else {
+        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+        bf16x2 o;
+        o[0] = (__bf16)lo;
+        o[1] = (__bf16)hi;
+        return __builtin_bit_cast(uint32_t, o);
+    }
+}
+
 // spmmGather over 16-bit source rows.  W: slice width in elements, as spmmGather; VE: elements per lane (8 = 16-byte
 // loads, 4 = 8-byte loads), G = W / VE lanes per unit, 64 / G units per wave.  A lane's load starts VE * 2 bytes into a
 // slice that starts W * 2 bytes into a row of K * 2 bytes (K a multiple of W, X 16-byte aligned): naturally aligned, and
 // the G loads of a unit cover one slice of one row.  v, the accumulators, the partials and Y are fp32.
-template <int W, int VE, bool MAP, int MODE>
+// YT = uint16_t: Y holds MODE's 16-bit format too; an item that owns its whole list rounds its sums and stores VE * 2
+// bytes per lane (8 or 16, aligned like the loads), a chunk of a split list still writes its fp32 partial.
+template <int W, int VE, bool MAP, int MODE, typename YT = float>
 __global__ void __launch_bounds__(256)
 spmmGather16(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSlices, const uint32_t* __restrict__ src,
              const uint32_t* __restrict__ map, const float* __restrict__ v, const uint16_t* __restrict__ X,
-             float* __restrict__ Y, float* __restrict__ partial, uint32_t K, uint64_t vBatch, uint64_t xBatch,
+             YT* __restrict__ Y, float* __restrict__ partial, uint32_t K, uint64_t vBatch, uint64_t xBatch,
              uint64_t yBatch, uint64_t pBatch) {
     constexpr int G = W / VE;
     constexpr int UPW = 64 / G;   // units per wave
@@ -210,12 +236,27 @@ spmmGather16(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSl
             bwFma16<MODE, VE>(wj, *reinterpret_cast<const T*>(xs + (uint64_t)sj * K), acc);
         }
     }
-    float* dst = (item.slot == kBwDirect ? Y + b * yBatch + (uint64_t)item.dest * K
-                                         : partial + b * pBatch + (uint64_t)item.slot * K) +
-                 (uint64_t)slice * W + (uint64_t)gl * VE;
+    if constexpr (sizeof(YT) == 2) {
+        const uint64_t col = (uint64_t)slice * W + (uint64_t)gl * VE;
+        if (item.slot == kBwDirect) {   // the one store of a finished row
+            T o;
 #pragma unroll
-    for (int i = 0; i < VE; i += 4)
-        *reinterpret_cast<float4*>(dst + i) = make_float4(acc[i], acc[i + 1], acc[i + 2], acc[i + 3]);
+            for (int i = 0; i < VE / 2; ++i) o[i] = bwNarrow<MODE>(acc[2 * i], acc[2 * i + 1]);
+            *reinterpret_cast<T*>(Y + b * yBatch + (uint64_t)item.dest * K + col) = o;
+        } else {
+            float* dst = partial + b * pBatch + (uint64_t)item.slot * K + col;
+#pragma unroll
+            for (int i = 0; i < VE; i += 4)
+                *reinterpret_cast<float4*>(dst + i) = make_float4(acc[i], acc[i + 1], acc[i + 2], acc[i + 3]);
+        }
+    } else {
+        float* dst = (item.slot == kBwDirect ? Y + b * yBatch + (uint64_t)item.dest * K
+                                             : partial + b * pBatch + (uint64_t)item.slot * K) +
+                     (uint64_t)slice * W + (uint64_t)gl * VE;
+#pragma unroll
+        for (int i = 0; i < VE; i += 4)
+            *reinterpret_cast<float4*>(dst + i) = make_float4(acc[i], acc[i + 1], acc[i + 2], acc[i + 3]);
+    }
 }
 
 // Y[dest] = partial[firstSlot] + partial[firstSlot + 1] + ... in chunk order; one thread per 4 floats of a split row.
@@ -237,6 +278,31 @@ spmmReduce(const BwSplit* __restrict__ splits, uint32_t numSplits, const float* 
         acc.w += x.w;
     }
     *reinterpret_cast<float4*>(Y + blockIdx.y * yBatch + (uint64_t)sp.dest * K + c) = acc;
+}
+
+// spmmReduce for a 16-bit Y: the same fp32 sum in chunk order, rounded once to MODE's format; 8 bytes per thread.
+template <int MODE>
+__global__ void __launch_bounds__(256)
+spmmReduce16(const BwSplit* __restrict__ splits, uint32_t numSplits, const float* __restrict__ partial,
+             uint16_t* __restrict__ Y, uint32_t K, uint64_t yBatch, uint64_t pBatch) {
+    const uint32_t q = K / 4u;
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= (uint64_t)numSplits * q) return;
+    const BwSplit sp = splits[i / q];
+    const uint64_t c = (i % q) * 4u;
+    const float* p = partial + blockIdx.y * pBatch + (uint64_t)sp.firstSlot * K + c;
+    float4 acc = *reinterpret_cast<const float4*>(p);
+    for (uint32_t k = 1; k < sp.numSlots; ++k) {
+        const float4 x = *reinterpret_cast<const float4*>(p + (uint64_t)k * K);
+        acc.x += x.x;
+        acc.y += x.y;
+        acc.z += x.z;
+        acc.w += x.w;
+    }
+    u32x2 o;
+    o[0] = bwNarrow<MODE>(acc.x, acc.y);
+    o[1] = bwNarrow<MODE>(acc.z, acc.w);
+    *reinterpret_cast<u32x2*>(Y + blockIdx.y * yBatch + (uint64_t)sp.dest * K + c) = o;
 }
 
 // vT[b][t] = v[b][map[t]]: the values in CSC order, once per call (the alternative to reading them through map).

@@ -215,6 +215,11 @@ HIP_SYMBOLS = {
                                            C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_spmm_lowp": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                  C.c_void_p]),
+    "bsmr_sddmm_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_spmm_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                               C.c_void_p]),
+    "bsmr_sddmm_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_sparse_softmax": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsmr_sparse_softmax_backward": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                C.c_void_p]),
@@ -753,6 +758,27 @@ def sddmm_backward(bw, K: int, dP_ptr: int, A_ptr: int, B_ptr: int, dA_ptr, dB_p
     else:
         _check(hip().bsmr_sddmm_backward_mode(bw, K, dP_ptr, A_ptr, B_ptr, dA_ptr or None, dB_ptr or None, num_batches,
                                               mode, stream), "bsmr_sddmm_backward_mode")
+
+
+# --- fp16 / bf16 tensors end to end: 16-bit operands in, 16-bit Y / dA / dB out; P, v and dP stay fp32 ---
+def sddmm_16(plan, K: int, A16_ptr: int, B16_ptr: int, P_ptr: int, num_batches: int = 1, mode=COMPUTE_F16, stream: int = 0):
+    """the forward on fp16 (mode F16) or bf16 (BF16) operands alone: no fp32 operand, no conversion pass"""
+    _check(hip().bsmr_sddmm_16(plan, K, A16_ptr or None, B16_ptr or None, P_ptr or None, num_batches, mode, stream),
+           "bsmr_sddmm_16")
+
+
+def spmm_16(bw, K: int, transpose: bool, v_ptr: int, X16_ptr: int, Y16_ptr: int, num_batches: int = 1, stream: int = 0,
+            mode=COMPUTE_F16):
+    """Y16 = round(S_v widen(X16)) (transpose True: S_v^T): 16-bit rows gathered, fp32 sums, one rounding per element"""
+    _check(hip().bsmr_spmm_16(bw, K, int(bool(transpose)), v_ptr or None, X16_ptr or None, Y16_ptr, num_batches, mode,
+                              stream), "bsmr_spmm_16")
+
+
+def sddmm_backward_16(bw, K: int, dP_ptr: int, A16_ptr: int, B16_ptr: int, dA16_ptr, dB16_ptr, num_batches: int = 1,
+                      stream: int = 0, mode=COMPUTE_F16):
+    """dA16 = round(S_dP widen(B16)), dB16 = round(S_dP^T widen(A16)); dA16_ptr / dB16_ptr None (or 0) skips that product"""
+    _check(hip().bsmr_sddmm_backward_16(bw, K, dP_ptr or None, A16_ptr or None, B16_ptr or None, dA16_ptr or None,
+                                        dB16_ptr or None, num_batches, mode, stream), "bsmr_sddmm_backward_16")
 
 
 def sparse_softmax(bw, scale: float, X_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0):

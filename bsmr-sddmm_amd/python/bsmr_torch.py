@@ -21,9 +21,20 @@ gather_mode (default COMPUTE_F32: every result bit for bit as without the argume
 read their operand rows: with COMPUTE_F16 / COMPUTE_BF16 spmm's X, the dY of its dX, and the B / A of sddmm's dA / dB are
 rounded once per call and gathered as 16-bit rows (half the bytes); values, sums and results stay fp32.  spmm then
 returns S_values round(X), and its dX is S_values^T round(dY): the gradients of the rounded-operand products.  The
-SDDMM calls (the forward, d values of spmm) follow `mode`, not gather_mode.  Tensors are fp32 in either case.
+SDDMM calls (the forward, d values of spmm) follow `mode`, not gather_mode.  Both arguments concern fp32 tensors only.
 
-Every call runs on torch.cuda.current_stream(device).  Operands are fp32, contiguous, on the operator's device, with
+Operand tensors (A / B, Q / Kt, X, V) may also be torch.float16 or torch.bfloat16, as a model under autocast holds them.
+The operands of one call share a dtype (a mix raises ValueError); attention's Q / Kt and V may differ, fp32 weights sit
+between them.  The format then follows the dtype, whatever `mode` and `gather_mode` say, and nothing is cast or copied:
+    sddmm:  P (fp32) = bsmr_sddmm_16(A, B), the fp32-accumulated products of the 16-bit values as they are;
+            dA, dB in the operands' dtype = bsmr_sddmm_backward_16: round(S_dP B), round(S_dP^T A)
+    spmm:   Y in X's dtype = bsmr_spmm_16: round(S_values X);  dX likewise from the transposed direction on dY (taken
+            in that dtype, not widened);  d values (fp32) = bsmr_sddmm_16(dY, X)
+Sums run in fp32 on the exactly widened rows and each output element is rounded once (round to nearest even).  The
+value tensors - `values`, P, the input and output of softmax - are fp32 only: scores and weights are never 16-bit.
+fp32 operands take the fp32 calls, bit for bit as before.
+
+Every call runs on torch.cuda.current_stream(device).  Operands are contiguous, on the operator's device, with
 K a positive multiple of 32; anything else raises ValueError.  Double backward is not supported.  Calls on one operator
 share its workspaces: issue them from one thread (the current stream orders them).
 """
@@ -35,6 +46,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 import bsmr_amd as eng
+
+
+_MODE16 = {torch.float16: eng.COMPUTE_F16, torch.bfloat16: eng.COMPUTE_BF16}   # the format follows the dtype
 
 
 class SparseOperator:
@@ -96,8 +110,8 @@ class SparseOperator:
         """batch None: either (rows, K) or (b, rows, K); returns (b or None, K)"""
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name}: expected a torch.Tensor")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name}: dtype {t.dtype}, expected torch.float32")
+        if t.dtype != torch.float32 and t.dtype not in _MODE16:
+            raise ValueError(f"{name}: dtype {t.dtype}, expected torch.float32, torch.float16 or torch.bfloat16")
         if t.device != self.device:
             raise ValueError(f"{name}: on {t.device}, the operator lives on {self.device}")
         if not t.is_contiguous():
@@ -116,6 +130,13 @@ class SparseOperator:
             raise ValueError(f"{name}: data not 16-byte aligned")
         return b, K
 
+    @staticmethod
+    def _mode16(a: torch.Tensor, b: torch.Tensor, names: str):
+        """the compute mode of a call on 16-bit operands, None for fp32 ones; the two must share a dtype"""
+        if a.dtype != b.dtype:
+            raise ValueError(f"{names}: dtypes {a.dtype} and {b.dtype}, the operands of one call share a dtype")
+        return _MODE16.get(a.dtype)
+
     def _check_values(self, v: torch.Tensor, b):
         if not isinstance(v, torch.Tensor):
             raise ValueError("values: expected a torch.Tensor")
@@ -129,9 +150,13 @@ class SparseOperator:
         _, K2 = self._check(B, "B", self.N, (b,))
         if K2 != K:
             raise ValueError(f"A and B disagree on K ({K} vs {K2})")
+        mode16 = self._mode16(A, B, "A and B")
         shape = (self.nnz,) if b is None else (b, self.nnz)
         P = torch.empty(shape, dtype=torch.float32, device=self.device)
         if self.nnz == 0:
+            return P
+        if mode16 is not None:
+            eng.sddmm_16(self._plan, K, A.data_ptr(), B.data_ptr(), P.data_ptr(), b or 1, mode16, self._stream())
             return P
         if b is None:
             eng.sddmm(self._plan, K, A.data_ptr(), B.data_ptr(), P.data_ptr(), self.mode, self._stream())
@@ -143,7 +168,11 @@ class SparseOperator:
         rows_x, rows_y = (self.M, self.N) if transpose else (self.N, self.M)
         b, K = self._check(X, "X", rows_x, None)
         self._check_values(v, b)
-        Y = torch.empty((rows_y, K) if b is None else (b, rows_y, K), dtype=torch.float32, device=self.device)
+        Y = torch.empty((rows_y, K) if b is None else (b, rows_y, K), dtype=X.dtype, device=self.device)
+        if X.dtype in _MODE16:
+            eng.spmm_16(self._bw, K, transpose, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
+                        mode=_MODE16[X.dtype])
+            return Y
         eng.spmm(self._bw, K, transpose, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
                  mode=self.gather_mode)
         return Y
@@ -180,15 +209,21 @@ class SparseOperator:
         b, K = self._check(A, "A", self.M, None)
         self._check(B, "B", self.N, (b,))
         self._check_values(dP, b)
+        mode16 = self._mode16(A, B, "A and B")
         dA = torch.empty_like(A) if need_a else None
         dB = torch.empty_like(B) if need_b else None
+        if mode16 is not None:
+            eng.sddmm_backward_16(self._bw, K, dP.data_ptr(), A.data_ptr(), B.data_ptr(), dA.data_ptr() if need_a else None,
+                                  dB.data_ptr() if need_b else None, b or 1, self._stream(), mode=mode16)
+            return dA, dB
         eng.sddmm_backward(self._bw, K, dP.data_ptr(), A.data_ptr(), B.data_ptr(), dA.data_ptr() if need_a else None,
                            dB.data_ptr() if need_b else None, b or 1, self._stream(), mode=self.gather_mode)
         return dA, dB
 
 
-def _grad(t: torch.Tensor) -> torch.Tensor:
-    return t.to(torch.float32).contiguous()
+def _grad(t: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """an incoming gradient, contiguous in `dtype` (a 16-bit gradient of a 16-bit output stays as it is: no widening)"""
+    return t.to(dtype).contiguous()
 
 
 class _SDDMM(torch.autograd.Function):
@@ -222,7 +257,7 @@ class _SpMM(torch.autograd.Function):
     def backward(ctx, dY):
         op, transpose = ctx.op, ctx.transpose
         values, X = ctx.saved_tensors
-        dY = _grad(dY)
+        dY = _grad(dY, X.dtype)
         dv = dX = None
         if ctx.needs_input_grad[1]:
             dv = op._sddmm(X, dY) if transpose else op._sddmm(dY, X)

@@ -38,6 +38,9 @@
  *                        <- no reference counterpart: Y = S_v X / S_v^T X and the two SDDMM gradients
  *   bsmr_spmm_mode / bsmr_sddmm_backward_mode / bsmr_spmm_lowp / bsmr_backward_reserve_mode
  *                        <- no reference counterpart: the same products with the gathered operand read as fp16 / bf16 rows
+ *   bsmr_sddmm_16 / bsmr_spmm_16 / bsmr_sddmm_backward_16
+ *                        <- no reference counterpart: the forward, the SpMM and the two gradients for a caller that holds
+ *                           fp16 / bf16 tensors only - 16-bit operands in, 16-bit Y / dA / dB out, the values stay fp32
  *   bsmr_sparse_softmax / bsmr_sparse_softmax_backward
  *                        <- no reference counterpart: the row softmax over S's pattern and its gradient
  *   bsmr_mem_info        <- cudaMemGetInfo in calculateBlockSize (src/rowReordering.cu:1010-1013)
@@ -439,12 +442,14 @@ int bsmr_plan_reserve(bsmr_plan *plan, uint32_t K);
  * below the alignment its argument needs (a NULL that the call allows counts as aligned):
  *   16 bytes  the operand matrices and their 16-bit copies: A_dev, B_dev (fp32, bsmr_sddmm, _batch, _timed, _lowp,
  *             bsmr_plan_tune, bsmr_convert_operands, bsmr_sddmm_backward[_mode]), A16_dev, B16_dev (bsmr_convert_operands,
- *             bsmr_sddmm_lowp), X_dev, Y_dev (bsmr_spmm[_mode]), X16_dev, Y_dev (bsmr_spmm_lowp), dA_dev, dB_dev
- *             (bsmr_sddmm_backward[_mode]).  The kernels move them 16 bytes at a time (global_load_dwordx4, LDS-DMA of 16
- *             bytes per lane, 16-byte stores of the conversion pass, float4 and 8 x 16-bit loads in the backward); K is a
- *             multiple of 32, so every row, column and batch then starts on 16 bytes.
+ *             bsmr_sddmm_lowp, bsmr_sddmm_16, bsmr_sddmm_backward_16), X_dev, Y_dev (bsmr_spmm[_mode]), X16_dev, Y_dev
+ *             (bsmr_spmm_lowp), X16_dev, Y16_dev (bsmr_spmm_16), dA_dev, dB_dev (bsmr_sddmm_backward[_mode]), dA16_dev,
+ *             dB16_dev (bsmr_sddmm_backward_16).  The kernels move them 16 bytes at a time (global_load_dwordx4, LDS-DMA of
+ *             16 bytes per lane, 16-byte stores of the conversion pass, float4 and 8 x 16-bit loads and stores in the
+ *             backward); K is a multiple of 32, so every row, column and batch then starts on 16 bytes.
  *    4 bytes  the value arrays, read and written one float at a time: P_dev (all of the above), v_dev (bsmr_spmm[_mode],
- *             bsmr_spmm_lowp), dP_dev (bsmr_sddmm_backward[_mode]), X_dev / Y_dev / dY_dev / dX_dev of bsmr_sparse_softmax[_backward], and
+ *             bsmr_spmm_lowp, bsmr_spmm_16), dP_dev (bsmr_sddmm_backward[_mode], bsmr_sddmm_backward_16), X_dev / Y_dev /
+ *             dY_dev / dX_dev of bsmr_sparse_softmax[_backward], and
  *             in_dev / out_dev of bsmr_batched_transpose.  A batch with an odd nnz puts its second problem on an odd
  *             float; that is within the contract.
  * No call reads or writes outside the extents its comment states (M K, N K, nnz elements, times num_batches), whatever
@@ -607,6 +612,46 @@ int bsmr_sddmm_backward_mode(bsmr_backward *bw, uint32_t K, const float *dP_dev,
                              float *dA_dev, float *dB_dev, uint32_t num_batches, int compute_mode, void *stream);
 int bsmr_spmm_lowp(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const void *X16_dev, float *Y_dev,
                    uint32_t num_batches, int compute_mode, void *stream);
+
+/* ---- fp16 / bf16 tensors end to end (revision 5, added without any layout change; no reference counterpart) ----
+ * For a caller that holds 16-bit tensors only (a model under autocast): no fp32 copy of an operand is read, made or
+ * written.  compute_mode is BSMR_COMPUTE_F16 or BSMR_COMPUTE_BF16 and says how every 16-bit array of the call is read and
+ * written; BSMR_COMPUTE_F32 is BSMR_ERR_INVALID_ARG.  The value arrays P, v and dP stay fp32: scores and softmax weights
+ * are never 16-bit.
+ *
+ * bsmr_sddmm_16: bsmr_sddmm_batch on the caller's 16-bit operands (A16 [b][M][K], B16 [b][N][K], P [b][nnz]; the batch in
+ * grid y; num_batches = 0 is a no-op, at most 65535 batches, K * num_batches below 2^32).  The dense part runs the 16-bit
+ * kernel of the engine the plan selects for (K, compute_mode), the residue always its 16-bit kernel - whatever sparse_lowp,
+ * convert_in_kernel, b_only, sweep_fp32 or gemm_fp32 say about the road of fp32 operands: no fp32 operand, no conversion
+ * pass and no operand workspace exist here (nothing to reserve; a tiles / sweep / GEMM format is still built on the first
+ * call that needs it).  Every entry is the fp32-accumulated product of the given 16-bit values: on a plan whose fp32 road
+ * runs the conversion pass, bit for bit what bsmr_sddmm_lowp returns for the same copies.  A hybrid plan overlaps its two
+ * kernels under the rule of bsmr_sddmm; a plan tuned with k_hint serves (K, compute_mode) with its variant.
+ *
+ * bsmr_spmm_16 / bsmr_sddmm_backward_16: the gather of bsmr_spmm_lowp (same lists, chunks, fma chains, lane layouts) with
+ * one addition - the single store of a finished destination row rounds to the 16-bit format (round to nearest even, fp16
+ * subnormals kept, +-inf beyond the range, NaN stays NaN: the casts of bsmr_convert_operands), 8 or 16 bytes per lane.
+ * Chunk partials stay fp32 in the workspace and are added in fp32: exactly one rounding per output element.
+ *   Y16 = round_mode(Y),  Y = the fp32 contract of "SDDMM backward" applied to (v, widen(X16)), bit for bit
+ * with all of its reproducibility: call to call, stream to stream, batch to batch, for any row_order, with or without
+ * BSMR_BACKWARD_PERMUTE, in either lane layout (BSMR_GATHER16_LANES).  A destination without entries is +0; a NaN in v
+ * reaches its destination row only.  bsmr_sddmm_backward_16: dA16 = round(S_dP widen(B16)) (M x K), dB16 =
+ * round(S_dP^T widen(A16)) (N x K); either output may be NULL: that product is skipped.  Neither call runs a conversion
+ * pass or uses the 16-bit region of the workspace: after bsmr_backward_reserve(K, num_batches) they allocate nothing and
+ * can be captured in a graph.
+ *
+ * Checked before any device work, in this order: a NULL plan / handle (BSMR_ERR_INVALID_ARG), K = 0 or not a multiple of
+ * 32 (BSMR_ERR_UNSUPPORTED_K), compute_mode, then the pointers: 16 bytes for every 16-bit array, 4 for the value arrays
+ * ("Alignment of device pointers").  With nnz = 0 the inputs may be NULL and the outputs are still all zeros
+ * (bsmr_sddmm_16 has nothing to write).  No call touches memory outside M K / N K 16-bit elements and nnz floats, times
+ * num_batches. */
+int bsmr_sddmm_16(bsmr_plan *plan, uint32_t K, const void *A16_dev, const void *B16_dev, float *P_dev,
+                  uint32_t num_batches, int compute_mode, void *stream);
+int bsmr_spmm_16(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const void *X16_dev,
+                 void *Y16_dev, uint32_t num_batches, int compute_mode, void *stream);
+int bsmr_sddmm_backward_16(bsmr_backward *bw, uint32_t K, const float *dP_dev, const void *A16_dev,
+                           const void *B16_dev, void *dA16_dev, void *dB16_dev, uint32_t num_batches,
+                           int compute_mode, void *stream);
 
 /* ---- Sparse row softmax (revision 5, added without any layout change; no reference counterpart) ----
  * The middle step of sparse attention (SDDMM -> softmax -> SpMM) on the same handle: values in S's CSR order, row r
