@@ -3752,3 +3752,4 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
 #include "colreorder_capi.hpp"
 #include "backward_capi.hpp"
 #include "softmax_capi.hpp"
+#include "attention_capi.hpp"

@@ -223,6 +223,14 @@ HIP_SYMBOLS = {
     "bsmr_sparse_softmax": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsmr_sparse_softmax_backward": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                C.c_void_p]),
+    "bsmr_sparse_attention_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "bsmr_sparse_attention": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]),
+    "bsmr_sparse_attention_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 5 +
+                                 [C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_backward": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
+                                       [C.c_uint32, C.c_void_p]),
+    "bsmr_sparse_attention_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
+                                          [C.c_uint32, C.c_int, C.c_void_p]),
 }
 
 HOST_SYMBOLS = {
@@ -790,3 +798,34 @@ def sparse_softmax_backward(bw, scale: float, Y_ptr: int, dY_ptr: int, dX_ptr: i
     """dX = (Y * (dY - rowsum(Y * dY))) * scale (dX may be dY)"""
     _check(hip().bsmr_sparse_softmax_backward(bw, scale, Y_ptr or None, dY_ptr or None, dX_ptr or None, num_batches,
                                               stream), "bsmr_sparse_softmax_backward")
+
+
+# --- fused sparse attention: O = softmax_rows(scale P) V in one gather, and its backward ---
+def sparse_attention_reserve(bw, Kv: int, num_batches: int = 1):
+    """workspace of sparse_attention / _backward (and of the spmm calls) with (Kv, num_batches)"""
+    _check(hip().bsmr_sparse_attention_reserve(bw, Kv, num_batches), "bsmr_sparse_attention_reserve")
+
+
+def sparse_attention(bw, Kv: int, scale: float, P_ptr: int, V_ptr: int, O_ptr: int, m_ptr: int, s_ptr: int,
+                     num_batches: int = 1, stream: int = 0, mode=COMPUTE_F32):
+    """O = softmax_rows(fl32(scale * P)) V, with the row maxima m and row sums s the backward needs; mode F16 / BF16: V
+    and O are 16-bit rows of that format (bsmr_sparse_attention_16)"""
+    if mode == COMPUTE_F32:
+        _check(hip().bsmr_sparse_attention(bw, Kv, scale, P_ptr or None, V_ptr or None, O_ptr or None, m_ptr or None,
+                                           s_ptr or None, num_batches, stream), "bsmr_sparse_attention")
+    else:
+        _check(hip().bsmr_sparse_attention_16(bw, Kv, scale, P_ptr or None, V_ptr or None, O_ptr or None, m_ptr or None,
+                                              s_ptr or None, num_batches, mode, stream), "bsmr_sparse_attention_16")
+
+
+def sparse_attention_backward(bw, Kv: int, scale: float, P_ptr: int, m_ptr: int, s_ptr: int, dW_ptr: int, O_ptr: int,
+                              dO_ptr: int, dP_ptr: int, W_ptr: int, num_batches: int = 1, stream: int = 0,
+                              mode=COMPUTE_F32):
+    """W = the softmax weights recomputed from (P, m, s); dP = (W * (dW - rowdot(dO, O))) * scale (dP may be dW); mode
+    F16 / BF16: O and dO are 16-bit rows of that format (bsmr_sparse_attention_backward_16)"""
+    args = (bw, Kv, scale, P_ptr or None, m_ptr or None, s_ptr or None, dW_ptr or None, O_ptr or None, dO_ptr or None,
+            dP_ptr or None, W_ptr or None, num_batches)
+    if mode == COMPUTE_F32:
+        _check(hip().bsmr_sparse_attention_backward(*args, stream), "bsmr_sparse_attention_backward")
+    else:
+        _check(hip().bsmr_sparse_attention_backward_16(*args, mode, stream), "bsmr_sparse_attention_backward_16")

@@ -5,9 +5,11 @@
     W = op.softmax(P, scale)                 # W = softmax of scale * P over each row of S   (nnz,) or (b, nnz)
     Y = op.spmm(values, X)                   # Y = S_values X     (transpose=True: S_values^T X)
     O = op.attention(Q, Kt, V)               # spmm(softmax(sddmm(Q, Kt), K**-0.5), V)
+    O = op.softmax_spmm(P, V, scale)         # softmax and spmm in one gather: the weights are never stored
+    O = op.attention(Q, Kt, V, fused=True)   # softmax_spmm(sddmm(Q, Kt), V, K**-0.5)
 
 All are torch.autograd.Functions whose backward runs on the engine (bsmr_sddmm_backward, bsmr_spmm, bsmr_sddmm,
-bsmr_sparse_softmax_backward), attention by composing the other three:
+bsmr_sparse_softmax_backward, bsmr_sparse_attention_backward), attention by composing the others:
     sddmm:    dA = S_dP B,  dB = S_dP^T A    (exact fp32 products of the given operands in every mode: the forward's
                                               operand rounding is treated as straight-through)
               with gather_mode = F16 / BF16:  dA = S_dP round(B),  dB = S_dP^T round(A) - the straight-through
@@ -15,7 +17,14 @@ bsmr_sparse_softmax_backward), attention by composing the other three:
                                               forward computes when `mode` is the same format
     softmax:  dX = (W * (dW - rowsum(W * dW))) * scale   (bsmr_sparse_softmax_backward: bitwise reproducible)
     spmm:     d values = sddmm(dY, X)  (transposed: sddmm(X, dY)),  dX = spmm(values, dY, not transpose)
-so SDDMM -> softmax -> SpMM, the usual sparse-attention layer, trains on the engine end to end.
+    softmax_spmm:  forward bsmr_sparse_attention, which also returns the row maxima m and row sums s; it saves
+              (values, X, m, s, O).  Backward: dW = sddmm(dO, X);  bsmr_sparse_attention_backward recomputes the weights W
+              from (values, m, s) and gives d values = (W * (dW - rowdot(dO, O))) * scale;  dX = spmm(W, dO, transposed).
+              Its sums run in another order than softmax followed by spmm, so the two paths agree to rounding, not in
+              bits (include/bsmr_hip.h "Fused sparse attention"); each is bitwise reproducible.  X follows spmm's dtype
+              rule: 16-bit X gives 16-bit O and dX, and D = rowdot(dO, O) is taken on the saved, rounded O.
+so SDDMM -> softmax -> SpMM, the usual sparse-attention layer, trains on the engine end to end.  attention(fused=True)
+takes the fused path; the default (fused=False) is the composition, unchanged.
 
 gather_mode (default COMPUTE_F32: every result bit for bit as without the argument) is the format in which the gathers
 read their operand rows: with COMPUTE_F16 / COMPUTE_BF16 spmm's X, the dY of its dX, and the B / A of sddmm's dA / dB are
@@ -91,12 +100,21 @@ class SparseOperator:
         entries are all -inf gives zeros, a NaN or +inf makes its row NaN, rows without entries hold nothing"""
         return _Softmax.apply(self, values, scale)
 
-    def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None) -> torch.Tensor:
+    def softmax_spmm(self, values: torch.Tensor, X: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+        """spmm(softmax(values, scale), X) in one gather (bsmr_sparse_attention): values (nnz,) or (b, nnz) fp32, X (N, K)
+        or (b, N, K) in fp32, fp16 or bf16 -> Y (M, K) in X's dtype.  A row of S without entries, or whose entries are
+        all -inf, gives a zero row; a NaN or +inf makes its row NaN."""
+        return _SoftmaxSpMM.apply(self, values, X, scale)
+
+    def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None, fused: bool = False) -> torch.Tensor:
         """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
-        positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row."""
+        positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row.
+        fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order."""
         P = self.sddmm(Q, Kt)
         if scale is None:
             scale = Q.shape[-1] ** -0.5
+        if fused:
+            return self.softmax_spmm(P, V, scale)
         return self.spmm(self.softmax(P, scale), V)
 
     def stats(self) -> dict:
@@ -205,6 +223,38 @@ class SparseOperator:
         eng.sparse_softmax_backward(self._bw, scale, Y.data_ptr(), dY.data_ptr(), dX.data_ptr(), b or 1, self._stream())
         return dX
 
+    def _attention(self, v: torch.Tensor, X: torch.Tensor, scale):
+        """(O, m, s) of the fused forward; O (M, K) or (b, M, K) in X's dtype, m and s (M,) or (b, M) fp32"""
+        b, K = self._check(X, "X", self.N, None)
+        _, scale = self._softmax_args(v, scale)
+        self._check_values(v, b)
+        O = torch.empty((self.M, K) if b is None else (b, self.M, K), dtype=X.dtype, device=self.device)
+        m = torch.empty((self.M,) if b is None else (b, self.M), dtype=torch.float32, device=self.device)
+        s = torch.empty_like(m)
+        eng.sparse_attention(self._bw, K, scale, v.data_ptr(), X.data_ptr(), O.data_ptr(), m.data_ptr(), s.data_ptr(), b or 1,
+                             self._stream(), mode=_MODE16.get(X.dtype, eng.COMPUTE_F32))
+        return O, m, s
+
+    def _attention_backward(self, v, m, s, dW, O, dO, scale):
+        """(dP, W) of the fused backward; dP is written over dW (the same tensor is returned)"""
+        b, K = self._check(O, "O", self.M, None)
+        self._check(dO, "dO", self.M, (b,))
+        if dO.shape != O.shape or dO.dtype != O.dtype:
+            raise ValueError(f"dO: {dO.dtype} {tuple(dO.shape)}, expected O's {O.dtype} {tuple(O.shape)}")
+        _, scale = self._softmax_args(v, scale)
+        self._check_values(v, b)
+        self._check_values(dW, b)
+        want = (self.M,) if b is None else (b, self.M)
+        for t, name in ((m, "m"), (s, "s")):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.device
+                    or not t.is_contiguous() or tuple(t.shape) != want):
+                raise ValueError(f"{name}: expected a contiguous float32 tensor of shape {want} on {self.device}")
+        W = torch.empty_like(v)
+        eng.sparse_attention_backward(self._bw, K, scale, v.data_ptr(), m.data_ptr(), s.data_ptr(), dW.data_ptr(),
+                                      O.data_ptr(), dO.data_ptr(), dW.data_ptr(), W.data_ptr(), b or 1, self._stream(),
+                                      mode=_MODE16.get(O.dtype, eng.COMPUTE_F32))
+        return dW, W
+
     def _sddmm_backward(self, dP, A, B, need_a: bool, need_b: bool):
         b, K = self._check(A, "A", self.M, None)
         self._check(B, "B", self.N, (b,))
@@ -281,6 +331,28 @@ class _Softmax(torch.autograd.Function):
             return None, None, None
         (Y,) = ctx.saved_tensors
         return None, ctx.op._softmax_backward(Y, _grad(dY), ctx.scale), None
+
+
+class _SoftmaxSpMM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, op: SparseOperator, values, X, scale):
+        O, m, s = op._attention(values, X, scale)
+        ctx.op, ctx.scale = op, float(scale)
+        ctx.save_for_backward(values, X, m, s, O)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        op = ctx.op
+        need_v, need_x = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (need_v or need_x):
+            return None, None, None, None
+        values, X, m, s, O = ctx.saved_tensors
+        dO = _grad(dO, X.dtype)
+        dP, W = op._attention_backward(values, m, s, op._sddmm(dO, X), O, dO, ctx.scale)
+        dX = op._spmm(W, dO, True) if need_x else None
+        return None, dP if need_v else None, dX, None
 
 
 __all__ = ["SparseOperator"]

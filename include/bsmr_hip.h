@@ -676,6 +676,52 @@ int bsmr_sparse_softmax(bsmr_backward *bw, float scale, const float *X_dev, floa
 int bsmr_sparse_softmax_backward(bsmr_backward *bw, float scale, const float *Y_dev, const float *dY_dev,
                                  float *dX_dev, uint32_t num_batches, void *stream);
 
+/* ---- Fused sparse attention: softmax . V in one gather (revision 5, added without any layout change) ----
+ * O = softmax_rows(scale P) V without the weights ever being stored: the softmax's row sum rides inside bsmr_spmm's row
+ * gather as one more accumulator.  Same handle, lists, chunks and lane layouts as bsmr_spmm (transpose 0); P [b][nnz] in
+ * S's CSR order, V [b][N][Kv], O [b][M][Kv], m and s [b][M].  Per row r of n entries, each step one IEEE fp32 operation
+ * (u = 2^-24):
+ *   forward   z_t = fl(scale p_t);  m = max_t z_t (any NaN z makes m NaN);  e_t = expf(fl(z_t - m)), the accurate expf,
+ *             and 0 when m = -inf;  s = sum_t e_t;  acc_k = sum_t fmaf(e_t, V[c_t,k], .);  O_k = acc_k / s (IEEE division)
+ *   s and acc run in bsmr_spmm's order: a sequential chain from +0 in CSR order; a row longer than BSMR_BACKWARD_CHUNK is
+ *   cut into the handle's chunks, and the partials of acc and of s are added in chunk order.
+ *   O_k is exactly +0 when m = -inf or the row is empty (then m = -inf, s = 0).  A NaN or +inf score makes its row of O
+ *   (and its m or s) NaN and no other; a row with one finite entry returns that row of V bit for bit (e = 1, s = 1).
+ *   backward  w_t = fl(e_t / s), e_t recomputed as above from (p_t, m, s), 0 when m = -inf;
+ *             D = dO_r . O_r in this order: lane l of 32 runs the fma chain fmaf(dO_k, O_k, .) over k = l, l + 32, ...
+ *             ascending from +0; the 32 partials are added by a butterfly over the lane offsets 16, 8, 4, 2, 1 (x + partner;
+ *             fp32 addition commutes, so all lanes hold the same bits);
+ *             dP_t = fl(fl(w_t fl(dW_t - D)) scale), with dW = sddmm(dO, V) from the caller;  W_t = w_t is written out
+ *             for the transposed bsmr_spmm that gives dV.  dP may alias dW.  D lives in the workspace.
+ * No atomics: bitwise reproducible call to call, stream to stream, batch to batch and for any row_order.
+ * Forward bound against fp64 over the same z (Z_r = max_j |z_j - m|, w64 the fp64 weights):
+ *   |O_k - O64_k| <= (2n + 2 Z_r + 10) u sum_t w64_t |V[c_t,k]| + (n + 2) 2^-126 max_t |V[c_t,k]|.
+ * W obeys the bound of y in "Sparse row softmax".
+ * The _16 forms: V, O, dO and the saved O are fp16 / bf16 rows (compute_mode BSMR_COMPUTE_F16 / _BF16, as in bsmr_spmm_16);
+ * P, m, s, dW, dP and W stay fp32.  Rows are widened exactly, sums are fp32, O16 = round(O) once (the casts of
+ * bsmr_convert_operands): bit for bit the fp32 call on widen(V16), rounded.  D is taken on the saved, ROUNDED O (the usual
+ * flash-attention choice): against the D of the unrounded O that moves it by at most u16 sum_k |dO_k| |O_k| (u16 = 2^-11
+ * fp16, 2^-8 bf16).
+ * bsmr_sparse_attention_reserve(Kv, num_batches): the workspace of the four calls - what bsmr_backward_reserve(Kv,
+ * num_batches) covers, and behind it the partial row sums and D; afterwards covered calls allocate nothing.
+ * Checked before any device call, in this order: a NULL handle or a non-finite scale (BSMR_ERR_INVALID_ARG), Kv = 0 or
+ * not a multiple of 32 (BSMR_ERR_UNSUPPORTED_K), compute_mode of a _16 call, more than 65535 batches, then the pointers:
+ * 16 bytes for V, O and dO, 4 for P, m, s, dW, dP and W.  num_batches = 0 is a no-op.  With nnz = 0 the inputs may be
+ * NULL; the forward still writes O = 0, m = -inf, s = 0. */
+int bsmr_sparse_attention_reserve(bsmr_backward *bw, uint32_t Kv, uint32_t num_batches);
+int bsmr_sparse_attention(bsmr_backward *bw, uint32_t Kv, float scale, const float *P_dev, const float *V_dev,
+                          float *O_dev, float *m_dev, float *s_dev, uint32_t num_batches, void *stream);
+int bsmr_sparse_attention_16(bsmr_backward *bw, uint32_t Kv, float scale, const float *P_dev, const void *V16_dev,
+                             void *O16_dev, float *m_dev, float *s_dev, uint32_t num_batches, int compute_mode,
+                             void *stream);
+int bsmr_sparse_attention_backward(bsmr_backward *bw, uint32_t Kv, float scale, const float *P_dev, const float *m_dev,
+                                   const float *s_dev, const float *dW_dev, const float *O_dev, const float *dO_dev,
+                                   float *dP_dev, float *W_dev, uint32_t num_batches, void *stream);
+int bsmr_sparse_attention_backward_16(bsmr_backward *bw, uint32_t Kv, float scale, const float *P_dev,
+                                      const float *m_dev, const float *s_dev, const float *dW_dev, const void *O16_dev,
+                                      const void *dO16_dev, float *dP_dev, float *W_dev, uint32_t num_batches,
+                                      int compute_mode, void *stream);
+
 /* Host operands in, host P out (upload, `iters` timed repetitions after one
  * warm-up, download).  ms_per_iter may be NULL. */
 int bsmr_sddmm_host(bsmr_plan *plan, uint32_t K, const float *A_host, const float *B_host,
