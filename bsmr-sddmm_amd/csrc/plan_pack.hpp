@@ -551,9 +551,21 @@ inline int packPlan(const bsmr_rphm_desc* d, const PackOptions& opt, PackedPlan&
         }
     } else {
         out.denseItems.clear();
-        for (uint32_t gi = 0; gi < G; ++gi)
-            for (uint32_t b = groupFirstBlock[gi]; b < groupFirstBlock[gi + 1]; b += perItem)
-                out.denseItems.push_back(DenseItem{gi, b, std::min(perItem, groupFirstBlock[gi + 1] - b), 0});
+        // (cut at perItem blocks and, like the staged items above, where a block starts outside the item's column span)
+        for (uint32_t gi = 0; gi < G; ++gi) {
+            uint32_t itemFirst = groupFirstBlock[gi], count = 0;
+            for (uint32_t b = groupFirstBlock[gi]; b < groupFirstBlock[gi + 1]; ++b) {
+                bool fits = count < perItem;
+                if (opt.itemSpan && count && out.blockCols[(size_t)b * 16] / opt.itemSpan != out.blockCols[(size_t)itemFirst * 16] / opt.itemSpan) fits = false;
+                if (!fits) {
+                    out.denseItems.push_back(DenseItem{gi, itemFirst, count, 0});
+                    count = 0;
+                }
+                if (count == 0) itemFirst = b;
+                ++count;
+            }
+            if (count) out.denseItems.push_back(DenseItem{gi, itemFirst, count, 0});
+        }
         out.rowBase = groupRowBase;
         out.winLen.clear();
         out.winMask.clear();

@@ -374,3 +374,37 @@ def outlier_row_pattern(groups=40, shared=64, long_row=2000, cols=8000, seed=7):
     ro = np.zeros(len(per_row) + 1, dtype=np.uint32)
     ro[1:] = np.cumsum([len(c) for c in per_row])
     return len(per_row), cols, ro, np.concatenate(per_row)
+
+
+def file_order_rows(sort):
+    """96 x 900, every seventh row 600 entries, columns in file order (tests/test_gpu_parity.py:
+    test_unsorted_csr_rows_fall_back_to_direct_scatter) or, with `sort`, ascending"""
+    rng = np.random.default_rng(3)
+    rows, cols = 96, 900
+    per_row = [rng.permutation(cols)[:600 if r % 7 == 0 else int(rng.integers(5, 120))] for r in range(rows)]
+    ro = np.zeros(rows + 1, np.uint32)
+    ro[1:] = np.cumsum([len(c) for c in per_row])
+    ci = np.concatenate([np.sort(c) if sort else c for c in per_row]).astype(np.uint32)
+    return rows, cols, ro, ci
+
+
+def window_pattern(F):
+    """One panel of 16 rows sharing columns 0-7 and 1000-1007; row 0 also holds F columns of its own, 8 .. 8 + F - 1,
+    which stay in the residue at delta = 0.3.  In row 0 the block of the 16 shared columns spans 16 + F - 1 positions of
+    P: 254 at F = 239 (the widest window), 255 at F = 240 (kWindowMax: too wide)."""
+    shared = np.concatenate([np.arange(8), np.arange(1000, 1008)])
+    per_row = [np.sort(np.concatenate([shared, np.arange(8, 8 + F)])) if r == 0 else shared for r in range(16)]
+    ro = np.zeros(17, np.uint32)
+    ro[1:] = np.cumsum([len(c) for c in per_row])
+    return 16, 1024, ro, np.concatenate(per_row).astype(np.uint32)
+
+
+def long_row_pattern(n):
+    """One row of n entries in shuffled column order and 15 short sorted rows, all dense at delta = 0: the largest offset
+    from a row's first dense entry is n - 1.  65 534 fits a 16-bit tile, 65 535 is its null value."""
+    rng = np.random.default_rng(9)
+    cols = n + 1
+    per_row = [rng.permutation(cols)[:n]] + [np.sort(rng.choice(cols, size=40, replace=False)) for _ in range(15)]
+    ro = np.zeros(17, np.uint32)
+    ro[1:] = np.cumsum([len(c) for c in per_row])
+    return 16, cols, ro, np.concatenate(per_row).astype(np.uint32)

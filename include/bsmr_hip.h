@@ -246,7 +246,11 @@ int bsmr_plan_options_default(bsmr_plan_options *opt);
 /* defaults, then every BSMR_<NAME> variable that is set */
 int bsmr_plan_options_from_env(bsmr_plan_options *opt);
 
-/* bsmr_plan_create = bsmr_plan_create_ex with bsmr_plan_options_from_env.  options == NULL: the defaults. */
+/* bsmr_plan_create = bsmr_plan_create_ex with bsmr_plan_options_from_env.  options == NULL: the defaults.
+ * Every stored entry needs one place in the RPHM arrays: a block cell or a residue entry.  A CSR that stores the same
+ * (row, column) twice keeps both copies only while that column is in the residue of the row's panel; where the column is
+ * dense there, its block cell holds one copy, the arrays no longer account for nnz entries and the plan is refused with
+ * BSMR_ERR_BAD_PLAN.  (The file loaders refuse such matrices; callers that build the CSR themselves must merge repeats.) */
 int bsmr_plan_create(bsmr_plan **out, int device, const bsmr_rphm_desc *desc);
 int bsmr_plan_create_ex(bsmr_plan **out, int device, const bsmr_rphm_desc *desc,
                         const bsmr_plan_options *options);

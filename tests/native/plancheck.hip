@@ -471,3 +471,388 @@ extern "C" int plancheck_evict(const bsmr_rphm_desc* d, uint64_t* out) {
     if (ev.evicted && after.numBlocks != before.numBlocks) return 23;
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The streaming format (csrc/plan_pack.hpp: packPlan / packResidue) read the way denseStream, denseGroups and their
+// fp32 / any-K / in-kernel-conversion siblings and the residue kernels read it (csrc/sddmm_kernels.hpp): every index a
+// kernel forms stays inside its array, and every CSR index is reached exactly once, from the tile cell of its own row
+// and column or from one residue entry.  The expected row and column of a CSR index come from the CSR itself.
+namespace {
+
+constexpr uint32_t kStreamNone = 0xFFFFFFFFu;
+
+int streamEncoding(const bsmr::PackedPlan& pk) {
+    return !pk.tilesMask.empty() ? 0 : !pk.tiles8.empty() ? 1 : !pk.tiles16.empty() ? 2 : !pk.tiles32.empty() ? 4 : 255;
+}
+
+// destination offset of accumulator element (lane, i) of tile t, as scatterTile decodes it; false: no entry
+bool streamDecode(const bsmr::PackedPlan& pk, int enc, size_t t, uint32_t lane, uint32_t i, uint32_t& off) {
+    const uint32_t g = lane >> 4, c = lane & 15u;
+    if (enc == 0) {
+        const uint32_t* w = &pk.tilesMask[t * 12 + g * 3];
+        const uint32_t m = ((i < 2 ? w[0] : w[1]) >> (16 * (i & 1))) & 0xFFFFu;
+        if (!((m >> c) & 1u)) return false;
+        off = ((w[2] >> (8 * i)) & 0xFFu) + (uint32_t)__builtin_popcount(m & ((1u << c) - 1u));
+        return true;
+    }
+    if (enc == 1) { off = pk.tiles8[t * 256 + lane * 4 + i]; return off != 0xFFu; }
+    if (enc == 2) { off = pk.tiles16[t * 256 + lane * 4 + i]; return off != 0xFFFFu; }
+    off = pk.tiles32[t * 256 + lane * 4 + i];
+    return off != 0xFFFFFFFFu;
+}
+
+struct StreamPlace {   // where the dense part computes a CSR index: launch position of the item, block, lane, register
+    uint32_t item = kStreamNone, block = kStreamNone, cell = kStreamNone;
+    bool operator==(const StreamPlace& o) const { return item == o.item && block == o.block && cell == o.cell; }
+};
+
+// Returns 0 or the number of the first violated invariant (1 .. 33).
+int streamCheck(const bsmr_rphm_desc* d, const uint32_t* ro, const uint32_t* ci, const bsmr::PackOptions& opt,
+                const bsmr::PackedPlan& pk, std::vector<StreamPlace>& place) {
+    const uint32_t H = pk.H, R = 16 * H, P = d->num_row_panels, G = pk.numGroups;
+    const int enc = streamEncoding(pk);
+    const bool windowed = enc == 0 || enc == 1;
+    const size_t numItems = pk.denseItems.size(), NB = pk.numBlocks;
+    place.assign(d->nnz, StreamPlace());
+    std::vector<uint32_t> rowOf(d->nnz);
+    for (uint32_t r = 0; r < d->M; ++r)
+        for (uint32_t t = ro[r]; t < ro[r + 1]; ++t) rowOf[t] = r;
+    // sizes of the arrays the kernels index
+    if (H != (opt.group == 2 || opt.group == 4 ? (uint32_t)opt.group : 1u) || G != (P + H - 1) / H) return 1;
+    if (pk.panelRows.size() != (size_t)P * 16 || pk.groupRows.size() != (size_t)G * R || pk.blockCols.size() != NB * 16 ||
+        pk.blockMask.size() != NB)
+        return 1;
+    if (NB && enc == 255) return 1;
+    if (enc != 255 && windowed != pk.staged) return 1;
+    if (NB) {
+        const size_t tiles = NB * H;
+        const size_t have = enc == 0 ? pk.tilesMask.size() / 12 : enc == 1 ? pk.tiles8.size() / 256 : enc == 2 ? pk.tiles16.size() / 256 : pk.tiles32.size() / 256;
+        if (have != tiles) return 1;
+        if (pk.rowBase.size() != (windowed ? numItems : (size_t)G) * R) return 1;
+        if (windowed && (pk.winLen.size() != numItems * R || pk.winMask.size() != numItems * R * (bsmr::kWindow / 32))) return 1;
+    }
+    for (const uint32_t row : pk.groupRows)
+        if (row >= d->M) return 33;   // (padding rows of a ragged last group are gathered from A like any other)
+    for (const uint32_t row : pk.panelRows)
+        if (row >= d->M) return 33;
+    // the blocks of every group, from the RPHM: its distinct dense columns, 16 to a block
+    std::vector<uint64_t> groupFirst((size_t)G + 1, 0);
+    {
+        std::vector<uint32_t> stamp((size_t)d->N + 1, 0);
+        for (uint32_t gi = 0; gi < G; ++gi) {
+            uint64_t distinct = 0;
+            for (uint32_t p = gi * H; p < std::min(P, (gi + 1) * H); ++p)
+                for (uint64_t i = (uint64_t)d->block_offsets[p] * 16; i < (uint64_t)d->block_offsets[p + 1] * 16; ++i) {
+                    const uint32_t col = d->dense_cols[i];
+                    if (col >= d->N || stamp[col] == gi + 1) continue;
+                    stamp[col] = gi + 1;
+                    ++distinct;
+                }
+            groupFirst[gi + 1] = groupFirst[gi] + (distinct + 15) / 16;
+        }
+    }
+    if (groupFirst[G] != NB) return 29;
+    std::vector<uint8_t> seen(d->nnz, 0), blockSeen(NB, 0);
+    uint64_t dense = 0;
+    std::vector<uint8_t> own((size_t)R * 256);
+    for (size_t it = 0; it < numItems; ++it) {
+        const bsmr::DenseItem& item = pk.denseItems[it];
+        if (item.count == 0 || item.group >= G || (uint64_t)item.first + item.count > NB) return 2;
+        if (item.count > (uint32_t)std::max(1, opt.blocksPerItem)) return 3;
+        if (item.first < groupFirst[item.group] || (uint64_t)item.first + item.count > groupFirst[item.group + 1]) return 29;
+        std::fill(own.begin(), own.end(), (uint8_t)0);
+        for (uint32_t b = item.first; b < item.first + item.count; ++b) {
+            if (blockSeen[b]++) return 4;
+            if (opt.itemSpan && pk.blockCols[(size_t)b * 16] / opt.itemSpan != pk.blockCols[(size_t)item.first * 16] / opt.itemSpan) return 30;
+            for (uint32_t c = 0; c < 16; ++c)
+                if (pk.blockCols[(size_t)b * 16 + c] >= d->N) return 5;
+            for (uint32_t k = 0; k < H; ++k) {
+                const bool masked = (pk.blockMask[b] >> k) & 1u;
+                const size_t t = (size_t)b * H + k;
+                uint32_t got = 0;
+                for (uint32_t lane = 0; lane < 64; ++lane)
+                    for (uint32_t i = 0; i < 4; ++i) {
+                        uint32_t off = 0;
+                        if (!streamDecode(pk, enc, t, lane, i, off)) continue;
+                        ++got;
+                        if (!masked) return 6;   // denseGroups and the one-wave kernels skip the tile: the entry is never computed
+                        const uint32_t row = k * 16 + 4 * (lane >> 4) + i, c = lane & 15u;
+                        uint64_t base;
+                        if (windowed) {
+                            const size_t slot = it * R + row;
+                            base = pk.rowBase[slot];
+                            if (off >= bsmr::kWindowMax || off >= pk.winLen[slot]) return 7;
+                            if (!((pk.winMask[slot * 8 + off / 32] >> (off % 32)) & 1u)) return 8;   // the LDS-staged form would not store it
+                            if (own[(size_t)row * 256 + off]++) return 9;
+                        } else {
+                            base = pk.rowBase[(size_t)item.group * R + row];
+                        }
+                        const uint64_t idx = base + off;
+                        if (idx >= d->nnz) return 10;
+                        if (pk.groupRows[(size_t)item.group * R + row] != rowOf[idx]) return 12;
+                        if (pk.blockCols[(size_t)b * 16 + c] != ci[idx]) return 13;
+                        if (seen[idx]++) return 11;
+                        place[idx].item = (uint32_t)it;
+                        place[idx].block = b;
+                        place[idx].cell = (k << 8) | (lane << 2) | i;
+                        ++dense;
+                    }
+                if (masked && !got) return 14;
+            }
+        }
+        if (windowed)
+            for (uint32_t row = 0; row < R; ++row) {
+                const size_t slot = it * R + row;
+                const uint32_t len = pk.winLen[slot];
+                if (len > bsmr::kWindowMax) return 15;
+                if (len && (uint64_t)pk.rowBase[slot] + len > d->nnz) return 16;
+                for (uint32_t j = 0; j < bsmr::kWindow; ++j) {
+                    const bool bit = (pk.winMask[slot * 8 + j / 32] >> (j % 32)) & 1u;
+                    if (bit && j >= len) return 18;
+                    if (bit != (own[(size_t)row * 256 + j] != 0)) return 17;   // a bit nobody wrote: stale LDS would reach P
+                }
+            }
+    }
+    for (size_t b = 0; b < NB; ++b)
+        if (!blockSeen[b]) return 19;
+    if (dense != pk.numDenseEntries) return 20;
+    // the residue, as sparseEntries / sparseEntriesLowp walk it
+    const uint64_t numSparse = pk.numSparseEntries;
+    if (pk.entryCol.size() != numSparse || pk.entryDst.size() != numSparse ||
+        (pk.freeResidue ? pk.entryRowId.size() : pk.entryRow.size()) != numSparse)
+        return 1;
+    uint64_t sparse = 0;
+    std::vector<uint8_t> entrySeen(numSparse, 0);
+    for (const bsmr::SparseItem& item : pk.sparseItems) {
+        if (item.count == 0 || item.count > (uint32_t)std::max(32, opt.sparsePerItem) || (uint64_t)item.start + item.count > numSparse) return 21;
+        if (pk.freeResidue ? item.panel != kStreamNone : item.panel >= P) return pk.freeResidue ? 23 : 24;
+        for (uint32_t e = item.start; e < item.start + item.count; ++e) {
+            if (entrySeen[e]++) return 22;
+            uint32_t row;
+            if (pk.freeResidue) {
+                row = pk.entryRowId[e];
+            } else {
+                if (pk.entryRow[e] >= 16) return 24;
+                row = pk.panelRows[(size_t)item.panel * 16 + pk.entryRow[e]];
+            }
+            const uint32_t idx = pk.entryDst[e];
+            if (idx >= d->nnz || seen[idx]) return 25;
+            seen[idx] = 1;
+            if (rowOf[idx] != row || ci[idx] != pk.entryCol[e] || pk.entryCol[e] >= d->N) return 26;
+            ++sparse;
+        }
+    }
+    if (sparse != numSparse) return 27;
+    for (uint32_t v = 0; v < d->nnz; ++v)
+        if (seen[v] != 1) return 28;
+    return 0;
+}
+
+// One deliberate defect in a packed plan (the proof that streamCheck can fail).  Returns false where the plan offers no
+// place for it.
+bool streamMutate(bsmr::PackedPlan& pk, int mutate) {
+    const uint32_t H = pk.H, R = 16 * H;
+    const int enc = streamEncoding(pk);
+    const bool windowed = enc == 0 || enc == 1;
+    const size_t numItems = pk.denseItems.size(), NB = pk.numBlocks;
+    switch (mutate) {
+    case 1:   // two offsets of one 8-bit tile row change places
+        if (enc != 1) return false;
+        for (size_t t = 0; t < NB * H; ++t)
+            for (uint32_t row = 0; row < 16; ++row) {
+                int first = -1;
+                for (uint32_t c = 0; c < 16; ++c) {
+                    const size_t at = t * 256 + ((row >> 2) * 16 + c) * 4 + (row & 3);
+                    if (pk.tiles8[at] == 0xFF) continue;
+                    if (first < 0) { first = (int)at; continue; }
+                    std::swap(pk.tiles8[(size_t)first], pk.tiles8[at]);
+                    return true;
+                }
+            }
+        return false;
+    case 2:   // a set blockMask bit cleared
+        for (size_t b = 0; b < NB; ++b)
+            if (pk.blockMask[b]) { pk.blockMask[b] &= (uint8_t)(pk.blockMask[b] - 1); return true; }
+        return false;
+    case 3:   // a clear blockMask bit (of a panel the kernels look at) set
+        for (size_t b = 0; b < NB; ++b)
+            for (uint32_t k = 0; k < H; ++k)
+                if (!((pk.blockMask[b] >> k) & 1u)) { pk.blockMask[b] |= (uint8_t)(1u << k); return true; }
+        return false;
+    case 4:   // a winMask bit inside a window that no tile of the item writes
+        if (!windowed) return false;
+        for (size_t slot = 0; slot < numItems * R; ++slot)
+            for (uint32_t j = 0; j < pk.winLen[slot]; ++j)
+                if (!((pk.winMask[slot * 8 + j / 32] >> (j % 32)) & 1u)) { pk.winMask[slot * 8 + j / 32] |= 1u << (j % 32); return true; }
+        return false;
+    case 5:   // an owned winMask bit cleared
+        if (!windowed) return false;
+        for (size_t w = 0; w < pk.winMask.size(); ++w)
+            if (pk.winMask[w]) { pk.winMask[w] &= pk.winMask[w] - 1; return true; }
+        return false;
+    case 6:   // a window one position shorter
+        if (!windowed) return false;
+        for (size_t slot = 0; slot < numItems * R; ++slot)
+            if (pk.winLen[slot]) { --pk.winLen[slot]; return true; }
+        return false;
+    case 7:   // a window base one entry further (a window of two or more entries: the shifted indices stay inside the CSR row)
+        if (!windowed) return false;
+        for (size_t slot = 0; slot < numItems * R; ++slot)
+            if (pk.winLen[slot] >= 2) { ++pk.rowBase[slot]; return true; }
+        return false;
+    case 8:   // two columns of a block change places (the first two: every stored column holds an entry)
+        for (size_t b = 0; b < NB; ++b)
+            if (pk.blockCols[b * 16] != pk.blockCols[b * 16 + 1]) { std::swap(pk.blockCols[b * 16], pk.blockCols[b * 16 + 1]); return true; }
+        return false;
+    case 9: { // two rows of a group change places: the rows of the first entry the dense part holds and of its neighbour
+        for (size_t it = 0; it < numItems; ++it) {
+            const bsmr::DenseItem& item = pk.denseItems[it];
+            for (uint32_t b = item.first; b < item.first + item.count; ++b)
+                for (uint32_t k = 0; k < H; ++k)
+                    for (uint32_t lane = 0; lane < 64; ++lane)
+                        for (uint32_t i = 0; i < 4; ++i) {
+                            uint32_t off;
+                            if (!streamDecode(pk, enc, (size_t)b * H + k, lane, i, off)) continue;
+                            const size_t row = (size_t)item.group * R + k * 16 + 4 * (lane >> 4) + i, other = row ^ 1u;
+                            if (pk.groupRows[row] == pk.groupRows[other]) continue;
+                            std::swap(pk.groupRows[row], pk.groupRows[other]);
+                            return true;
+                        }
+        }
+        return false;
+    }
+    case 10: {  // the per-item arrays of two items of one group change places (a wrong permutation in the item sort)
+        if (!windowed) return false;
+        for (size_t a = 0; a < numItems; ++a)
+            for (size_t b = a + 1; b < numItems; ++b) {
+                if (pk.denseItems[a].group != pk.denseItems[b].group) continue;
+                if (std::equal(pk.rowBase.begin() + a * R, pk.rowBase.begin() + (a + 1) * R, pk.rowBase.begin() + b * R)) continue;
+                std::swap_ranges(pk.rowBase.begin() + a * R, pk.rowBase.begin() + (a + 1) * R, pk.rowBase.begin() + b * R);
+                std::swap_ranges(pk.winLen.begin() + a * R, pk.winLen.begin() + (a + 1) * R, pk.winLen.begin() + b * R);
+                std::swap_ranges(pk.winMask.begin() + a * R * 8, pk.winMask.begin() + (a + 1) * R * 8, pk.winMask.begin() + b * R * 8);
+                return true;
+            }
+        return false;
+    }
+    case 11:  // a residue entry repeated in place of its neighbour
+        for (const bsmr::SparseItem& item : pk.sparseItems) {
+            if (item.count < 2) continue;
+            const uint32_t e = item.start;
+            if (pk.entryDst[e + 1] == pk.entryDst[e]) continue;
+            pk.entryDst[e + 1] = pk.entryDst[e];
+            pk.entryCol[e + 1] = pk.entryCol[e];
+            if (pk.freeResidue) pk.entryRowId[e + 1] = pk.entryRowId[e];
+            else pk.entryRow[e + 1] = pk.entryRow[e];
+            return true;
+        }
+        return false;
+    case 12:  // mask form: the first offset of a tile row with two or more entries, plus one
+    case 13:  // mask form: one bit of a tile row's column mask moved to the free column next to it
+        if (enc != 0) return false;
+        for (size_t t = 0; t < NB * H; ++t)
+            for (uint32_t row = 0; row < 16; ++row) {
+                uint32_t* w = &pk.tilesMask[t * 12 + (row >> 2) * 3];
+                const uint32_t i = row & 3u, shift = 16 * (i & 1);
+                uint32_t& word = i < 2 ? w[0] : w[1];
+                const uint32_t m = (word >> shift) & 0xFFFFu;
+                if (mutate == 12) {
+                    if (__builtin_popcount(m) < 2 || ((w[2] >> (8 * i)) & 0xFFu) >= 0xFEu) continue;
+                    w[2] += 1u << (8 * i);
+                    return true;
+                }
+                const size_t b = t / H;
+                for (uint32_t c = 0; c + 1 < 16; ++c)
+                    if (((m >> c) & 3u) == 1u && pk.blockCols[b * 16 + c] != pk.blockCols[b * 16 + c + 1]) {
+                        word ^= 3u << (shift + c);
+                        return true;
+                    }
+            }
+        return false;
+    default: return false;
+    }
+}
+
+// FNV-1a over every array of the plan a kernel reads
+uint64_t streamDigest(const bsmr::PackedPlan& pk) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto add = [&h](const void* ptr, size_t bytes) {
+        const uint8_t* b = static_cast<const uint8_t*>(ptr);
+        for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+    };
+    auto vec = [&add](const auto& v) { add(v.data(), v.size() * sizeof(v[0])); };
+    vec(pk.panelRows); vec(pk.groupRows); vec(pk.rowBase); vec(pk.winLen); vec(pk.winMask); vec(pk.blockCols);
+    vec(pk.tiles8); vec(pk.tilesMask); vec(pk.tiles16); vec(pk.tiles32); vec(pk.blockMask); vec(pk.denseItems);
+    vec(pk.entryCol); vec(pk.entryDst); vec(pk.entryRow); vec(pk.entryRowId); vec(pk.sparseItems);
+    return h;
+}
+
+}  // namespace
+
+// options: [0] group, [1] blocksPerItem, [2] sparsePerItem, [3] forceWideTiles, [4] columnOrder, [5] staged, [6] maskTiles,
+// [7] freeResidue, [8] itemOrder, [9] orderWindow, [10] itemSpan (the fields of bsmr::PackOptions).  promote / evict: run
+// promoteSparseBlocks (a panel's residue averaging 16 entries per block, no other condition) / evictWideRows on the arrays
+// first.  mutate: 0, or one of streamMutate's defects, applied between packing and checking.
+// out[0] encoding (0 mask form, 1 8-bit windows, 2 / 4 bytes per direct offset, 255 no dense tiles), [1] dense items,
+// [2] blocks, [3] dense entries, [4] residue entries, [5] residue items, [6] staged, [7] tooWide, [8] promoted entries,
+// [9] evicted entries, [10] the mutation changed the plan (a digest of its arrays before and after), [11] packPlan status, [12] blocks of the largest dense item.
+// Returns 0; 1 .. 33 the first violated invariant (streamCheck); 31 the mask form and the 8-bit form of the same options
+// disagree on where an entry is computed, 32 the 8-bit form itself is wrong; 200 + status when packPlan refuses the arrays;
+// 300 + status from evictWideRows; 900 when the plan has no place for the mutation.
+extern "C" int plancheck_stream(const bsmr_rphm_desc* d, const uint32_t* rowOffsets, const uint32_t* colIndices, const int32_t* options,
+                                int promote, int evict, int mutate, uint64_t* out) {
+    bsmr::PackOptions opt;
+    opt.group = options[0];
+    opt.blocksPerItem = options[1];
+    opt.sparsePerItem = options[2];
+    opt.forceWideTiles = options[3] != 0;
+    opt.columnOrder = options[4] != 0;
+    opt.staged = options[5] != 0;
+    opt.maskTiles = options[6] != 0;
+    opt.freeResidue = options[7];
+    opt.itemOrder = options[8];
+    opt.orderWindow = (uint32_t)options[9];
+    opt.itemSpan = (uint32_t)options[10];
+    for (int i = 0; i < 13; ++i) out[i] = 0;
+    bsmr::PromotedRphm pr;
+    bsmr::EvictedRphm ev;
+    if (promote && bsmr::promoteSparseBlocks(*d, 16, 0, 0, 0, 0, pr)) {
+        d = &pr.desc;
+        out[8] = pr.promotedEntries;
+    }
+    if (evict) {
+        if (const int st = bsmr::evictWideRows(d, ev)) return 300 + st;
+        if (ev.evicted) d = &ev.desc;
+        out[9] = ev.evicted;
+    }
+    bsmr::PackedPlan pk;
+    const int st = bsmr::packPlan(d, opt, pk);
+    out[11] = (uint64_t)(int64_t)st;
+    if (st != BSMR_OK) return 200 + st;
+    out[0] = (uint64_t)streamEncoding(pk);
+    out[1] = pk.denseItems.size();
+    out[2] = pk.numBlocks;
+    out[3] = pk.numDenseEntries;
+    out[4] = pk.numSparseEntries;
+    out[5] = pk.sparseItems.size();
+    out[6] = pk.staged;
+    out[7] = pk.tooWide;
+    for (const bsmr::DenseItem& item : pk.denseItems) out[12] = std::max<uint64_t>(out[12], item.count);
+    if (mutate) {
+        const uint64_t before = streamDigest(pk);
+        if (!streamMutate(pk, mutate)) return 900;
+        out[10] = streamDigest(pk) != before;   // the defect really is in the arrays the check reads
+        if (!out[10]) return 900;
+    }
+    std::vector<StreamPlace> place;
+    if (const int rc = streamCheck(d, rowOffsets, colIndices, opt, pk, place)) return rc;
+    if (streamEncoding(pk) == 0) {   // the same options without the mask form: the same place for every entry
+        bsmr::PackOptions plain = opt;
+        plain.maskTiles = false;
+        bsmr::PackedPlan pk8;
+        if (bsmr::packPlan(d, plain, pk8) != BSMR_OK || streamEncoding(pk8) != 1) return 32;
+        std::vector<StreamPlace> place8;
+        if (streamCheck(d, rowOffsets, colIndices, plain, pk8, place8)) return 32;
+        if (!(place == place8)) return 31;
+    }
+    return 0;
+}

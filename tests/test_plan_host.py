@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import synth
+from rphm_desc import pipeline_desc
 
 REPO = Path(__file__).resolve().parent.parent
 
@@ -19,21 +20,7 @@ def plancheck(engine):
     lib.plancheck_promote.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
 
     def run(rows, cols, ro, ci, alpha, delta, min_average=16, min_entries=1_000_000, small_dense=32768, column_degree=32, head=0):
-        csr = engine.CSR.from_arrays(rows, cols, ro, ci)
-        pipe = engine.Pipeline(csr, alpha=alpha, delta=delta, device=-1)
-        arrays = pipe.arrays()
-        keep = {k: np.ascontiguousarray(arrays[k], dtype=np.uint32) for k in
-                ("reorderedRows", "denseCols", "blockOffsets", "blockValues", "sparseValueOffsets",
-                 "sparseValues", "sparseRelativeRows", "sparseColIndices")}
-        d = engine.RphmDesc()
-        d.M, d.N, d.nnz = rows, cols, csr.nnz
-        d.num_nonzero_rows = keep["reorderedRows"].size
-        d.num_row_panels = keep["blockOffsets"].size - 1
-        cast = lambda a: a.ctypes.data_as(engine.u32p)
-        d.reordered_rows, d.dense_cols = cast(keep["reorderedRows"]), cast(keep["denseCols"])
-        d.block_offsets, d.block_values = cast(keep["blockOffsets"]), cast(keep["blockValues"])
-        d.sparse_value_offsets, d.sparse_values = cast(keep["sparseValueOffsets"]), cast(keep["sparseValues"])
-        d.sparse_relative_rows, d.sparse_col_indices = cast(keep["sparseRelativeRows"]), cast(keep["sparseColIndices"])
+        csr, d, keep = pipeline_desc(engine, rows, cols, ro, ci, alpha, delta)
         out = (C.c_uint64 * 13)()
         rc = lib.plancheck_promote(C.byref(d), min_average, min_entries, small_dense, column_degree, head, out)
         names = ("promoted", "promoted_entries", "promoted_blocks", "blocks", "residue", "pack_status", "packed_dense",
@@ -53,21 +40,7 @@ def tilecheck(engine):
     lib.plancheck_tiles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
 
     def run(rows, cols, ro, ci, alpha, delta, H, blocks_per_item):
-        csr = engine.CSR.from_arrays(rows, cols, ro, ci)
-        pipe = engine.Pipeline(csr, alpha=alpha, delta=delta, device=-1)
-        arrays = pipe.arrays()
-        keep = {k: np.ascontiguousarray(arrays[k], dtype=np.uint32) for k in
-                ("reorderedRows", "denseCols", "blockOffsets", "blockValues", "sparseValueOffsets",
-                 "sparseValues", "sparseRelativeRows", "sparseColIndices")}
-        d = engine.RphmDesc()
-        d.M, d.N, d.nnz = rows, cols, csr.nnz
-        d.num_nonzero_rows = keep["reorderedRows"].size
-        d.num_row_panels = keep["blockOffsets"].size - 1
-        cast = lambda a: a.ctypes.data_as(engine.u32p)
-        d.reordered_rows, d.dense_cols = cast(keep["reorderedRows"]), cast(keep["denseCols"])
-        d.block_offsets, d.block_values = cast(keep["blockOffsets"]), cast(keep["blockValues"])
-        d.sparse_value_offsets, d.sparse_values = cast(keep["sparseValueOffsets"]), cast(keep["sparseValues"])
-        d.sparse_relative_rows, d.sparse_col_indices = cast(keep["sparseRelativeRows"]), cast(keep["sparseColIndices"])
+        csr, d, keep = pipeline_desc(engine, rows, cols, ro, ci, alpha, delta)
         out = (C.c_uint64 * 11)()
         rc = lib.plancheck_tiles(C.byref(d), H, blocks_per_item, out)
         names = ("blocks", "tiles", "union_columns", "entries", "items", "entry_cap", "bytes", "census_blocks",
@@ -167,21 +140,7 @@ def sweepcheck(engine):
     lib.plancheck_sweep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
 
     def run(rows, cols, ro, ci, alpha, delta, panels_per_wave, strip_blocks, waves=4):
-        csr = engine.CSR.from_arrays(rows, cols, ro, ci)
-        pipe = engine.Pipeline(csr, alpha=alpha, delta=delta, device=-1)
-        arrays = pipe.arrays()
-        keep = {k: np.ascontiguousarray(arrays[k], dtype=np.uint32) for k in
-                ("reorderedRows", "denseCols", "blockOffsets", "blockValues", "sparseValueOffsets",
-                 "sparseValues", "sparseRelativeRows", "sparseColIndices")}
-        d = engine.RphmDesc()
-        d.M, d.N, d.nnz = rows, cols, csr.nnz
-        d.num_nonzero_rows = keep["reorderedRows"].size
-        d.num_row_panels = keep["blockOffsets"].size - 1
-        cast = lambda a: a.ctypes.data_as(engine.u32p)
-        d.reordered_rows, d.dense_cols = cast(keep["reorderedRows"]), cast(keep["denseCols"])
-        d.block_offsets, d.block_values = cast(keep["blockOffsets"]), cast(keep["blockValues"])
-        d.sparse_value_offsets, d.sparse_values = cast(keep["sparseValueOffsets"]), cast(keep["sparseValues"])
-        d.sparse_relative_rows, d.sparse_col_indices = cast(keep["sparseRelativeRows"]), cast(keep["sparseColIndices"])
+        csr, d, keep = pipeline_desc(engine, rows, cols, ro, ci, alpha, delta)
         out = (C.c_uint64 * 6)()
         rc = lib.plancheck_sweep(C.byref(d), waves, panels_per_wave, strip_blocks, out)
         res = dict(zip(("items", "entries", "groups", "strips", "max_step_entries", "bytes"), (int(v) for v in out)))
@@ -237,21 +196,9 @@ def gemmcheck(engine):
     lib.plancheck_gemm.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
 
     def run(rows, cols, ro, ci, alpha, delta, panels, blocks, balance=1, nnz=None):
-        csr = engine.CSR.from_arrays(rows, cols, ro, ci)
-        pipe = engine.Pipeline(csr, alpha=alpha, delta=delta, device=-1)
-        arrays = pipe.arrays()
-        keep = {k: np.ascontiguousarray(arrays[k], dtype=np.uint32) for k in
-                ("reorderedRows", "denseCols", "blockOffsets", "blockValues", "sparseValueOffsets",
-                 "sparseValues", "sparseRelativeRows", "sparseColIndices")}
-        d = engine.RphmDesc()
-        d.M, d.N, d.nnz = rows, cols, csr.nnz if nnz is None else nnz   # (nnz: a larger P than the pattern's)
-        d.num_nonzero_rows = keep["reorderedRows"].size
-        d.num_row_panels = keep["blockOffsets"].size - 1
-        cast = lambda a: a.ctypes.data_as(engine.u32p)
-        d.reordered_rows, d.dense_cols = cast(keep["reorderedRows"]), cast(keep["denseCols"])
-        d.block_offsets, d.block_values = cast(keep["blockOffsets"]), cast(keep["blockValues"])
-        d.sparse_value_offsets, d.sparse_values = cast(keep["sparseValueOffsets"]), cast(keep["sparseValues"])
-        d.sparse_relative_rows, d.sparse_col_indices = cast(keep["sparseRelativeRows"]), cast(keep["sparseColIndices"])
+        csr, d, keep = pipeline_desc(engine, rows, cols, ro, ci, alpha, delta)
+        if nnz is not None:
+            d.nnz = nnz                              # (a larger P than the pattern's)
         out = (C.c_uint64 * 11)()
         rc = lib.plancheck_gemm(C.byref(d), panels, blocks, balance, out)
         res = dict(zip(("items", "entries", "groups", "strips", "full_grid", "bytes", "tiles", "longest_list", "fullest_strip", "emptiest_strip", "lopsided"),
@@ -346,20 +293,7 @@ def evictcheck(engine):
     lib.plancheck_evict.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 
     def run(rows, cols, ro, ci, alpha, delta):
-        csr = engine.CSR.from_arrays(rows, cols, ro, ci)
-        arrays = engine.Pipeline(csr, alpha=alpha, delta=delta, device=-1).arrays()
-        keep = {k: np.ascontiguousarray(arrays[k], dtype=np.uint32) for k in
-                ("reorderedRows", "denseCols", "blockOffsets", "blockValues", "sparseValueOffsets",
-                 "sparseValues", "sparseRelativeRows", "sparseColIndices")}
-        d = engine.RphmDesc()
-        d.M, d.N, d.nnz = rows, cols, csr.nnz
-        d.num_nonzero_rows = keep["reorderedRows"].size
-        d.num_row_panels = keep["blockOffsets"].size - 1
-        cast = lambda a: a.ctypes.data_as(engine.u32p)
-        d.reordered_rows, d.dense_cols = cast(keep["reorderedRows"]), cast(keep["denseCols"])
-        d.block_offsets, d.block_values = cast(keep["blockOffsets"]), cast(keep["blockValues"])
-        d.sparse_value_offsets, d.sparse_values = cast(keep["sparseValueOffsets"]), cast(keep["sparseValues"])
-        d.sparse_relative_rows, d.sparse_col_indices = cast(keep["sparseRelativeRows"]), cast(keep["sparseColIndices"])
+        csr, d, keep = pipeline_desc(engine, rows, cols, ro, ci, alpha, delta)
         out = (C.c_uint64 * 7)()
         rc = lib.plancheck_evict(C.byref(d), out)
         return rc, dict(zip(("wide_before", "evicted", "wide_after", "tile_bytes", "dense", "residue", "dense_before"), (int(v) for v in out)))
