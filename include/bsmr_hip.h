@@ -542,7 +542,10 @@ int bsmr_sharded_sddmm_host(bsmr_sharded *s, uint32_t K, const float *A_host, co
  * a sequential fp32 fma chain; a list longer than BSMR_BACKWARD_CHUNK is summed chunk by chunk and the partials are added
  * in chunk order.  No atomics: results are bitwise reproducible call to call, stream to stream, batch to batch and for
  * any row_order; a destination without entries is exactly 0; |Y - Y_exact| <= (n + 2) u sum|v||x| (n = list length,
- * u = 2^-24).  The chunk partials live in a workspace of the handle: calls on one handle are ordered by the caller. */
+ * u = 2^-24).  The chunk partials live in a workspace of the handle: calls on one handle are ordered by the caller.
+ * Extents: every element index - s K of a source row, dest K of a destination row, the batch offsets b rows K and b nnz,
+ * b slots K + slot K of a workspace row - is formed in 64 bits; M K, N K, nnz and slots K, each times num_batches, may
+ * pass 2^32 elements (tests/test_gpu_backward_extents.py drives each of them past 2^32 elements, not only past 4 GiB). */
 #define BSMR_BACKWARD_CHUNK 512u   /* entries per work item of a long list (cdna_hip_programming.md, Appendix B) */
 typedef struct bsmr_backward bsmr_backward;
 typedef struct bsmr_backward_stats {
@@ -648,7 +651,9 @@ int bsmr_spmm_lowp(bsmr_backward *bw, uint32_t K, int transpose, const float *v_
  * 32 (BSMR_ERR_UNSUPPORTED_K), compute_mode, then the pointers: 16 bytes for every 16-bit array, 4 for the value arrays
  * ("Alignment of device pointers").  With nnz = 0 the inputs may be NULL and the outputs are still all zeros
  * (bsmr_sddmm_16 has nothing to write).  No call touches memory outside M K / N K 16-bit elements and nnz floats, times
- * num_batches. */
+ * num_batches.  The gathers of this section and of the gather modes above index like "SDDMM backward": 16-bit rows are
+ * read and stored at element indices past 2^32 (8 GiB), and the copies the _mode calls make may hold more than 2^32
+ * elements each (tests/test_gpu_backward_extents.py, case R). */
 int bsmr_sddmm_16(bsmr_plan *plan, uint32_t K, const void *A16_dev, const void *B16_dev, float *P_dev,
                   uint32_t num_batches, int compute_mode, void *stream);
 int bsmr_spmm_16(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const void *X16_dev,
@@ -674,7 +679,8 @@ int bsmr_sddmm_backward_16(bsmr_backward *bw, uint32_t K, const float *dP_dev, c
  *   |y_t - y64_t| <= (n + 6 + |z_t - m| + Z_r) u y64_t + (n + 2) 2^-126,   |sum_t y_t - 1| <= (n + 6) u + (n + 2) 2^-126.
  * Batches: values [b][nnz], the batch in grid y (b <= 65535).  Y may alias X, dX may alias dY.  num_batches = 0 is a
  * no-op; a NULL handle, a non-finite scale or a NULL array with nnz > 0 is BSMR_ERR_INVALID_ARG; with nnz = 0 the arrays
- * may be NULL.  Neither call allocates (no workspace): both can be captured in a graph. */
+ * may be NULL.  Neither call allocates (no workspace): both can be captured in a graph.  b nnz is formed in 64 bits:
+ * num_batches * nnz may pass 2^32 entries (tests/test_gpu_backward_extents.py, case V). */
 int bsmr_sparse_softmax(bsmr_backward *bw, float scale, const float *X_dev, float *Y_dev,
                         uint32_t num_batches, void *stream);
 int bsmr_sparse_softmax_backward(bsmr_backward *bw, float scale, const float *Y_dev, const float *dY_dev,
@@ -711,7 +717,9 @@ int bsmr_sparse_softmax_backward(bsmr_backward *bw, float scale, const float *Y_
  * Checked before any device call, in this order: a NULL handle or a non-finite scale (BSMR_ERR_INVALID_ARG), Kv = 0 or
  * not a multiple of 32 (BSMR_ERR_UNSUPPORTED_K), compute_mode of a _16 call, more than 65535 batches, then the pointers:
  * 16 bytes for V, O and dO, 4 for P, m, s, dW, dP and W.  num_batches = 0 is a no-op.  With nnz = 0 the inputs may be
- * NULL; the forward still writes O = 0, m = -inf, s = 0. */
+ * NULL; the forward still writes O = 0, m = -inf, s = 0.  (b M + r) Kv, b nnz and (b slots + slot) Kv are formed in 64
+ * bits: O, the value arrays and the workspace may each pass 2^32 elements (tests/test_gpu_backward_extents.py, cases O,
+ * S and V). */
 int bsmr_sparse_attention_reserve(bsmr_backward *bw, uint32_t Kv, uint32_t num_batches);
 int bsmr_sparse_attention(bsmr_backward *bw, uint32_t Kv, float scale, const float *P_dev, const float *V_dev,
                           float *O_dev, float *m_dev, float *s_dev, uint32_t num_batches, void *stream);

@@ -484,7 +484,9 @@ def _far_pattern(M, N, seed):
 def test_addresses_past_4gib(engine, oracle, nb, N):
     """dA = S_dP B reads rows of B past 4 GiB (one batch: B is N x 1024 fp32 = 4.5 GB; two batches of 2.3 GB: batch 1's
     rows start 2.3 GB in); dB = S_dP^T A writes rows past 4 GiB of its N x K output.  B is generated on the device and
-    only the rows read come back; dB is checked on the far rows that have entries and on far rows that have none."""
+    only the rows read come back; dB is checked on the far rows that have entries and on far rows that have none.
+    This covers byte offsets: every element index stays below 2^31 (1.13 - 1.15 x 2^30 elements); the cases whose element
+    indices pass 2^32 live in tests/test_gpu_backward_extents.py."""
     M, K = 64, 1024
     x_bytes = nb * N * K * 4
     need = 2 * x_bytes + (4 << 30)

@@ -260,7 +260,9 @@ def test_empty_pattern_with_null_pointers(engine):
 
 # ---- 5. a batch past 2^30 floats -----------------------------------------------------------------------------------
 def test_large_batch_past_4gib(engine, pats):
-    """b * nnz > 2^30: values past 4 GiB (the last batches' offsets need 64 bits) match the per-batch result"""
+    """b * nnz > 2^30: values past 4 GiB (the last batches' offsets need 64 bits) match the per-batch result.  This covers
+    byte offsets: b * nnz stays below 2^31 entries; b * nnz past 2^32 entries is case V of
+    tests/test_gpu_backward_extents.py."""
     p = pats("lengths")
     nb = (1 << 30) // p.nnz + 2
     assert nb * p.nnz > 1 << 30 and nb <= 65535
