@@ -10,7 +10,30 @@
 // Included at the end of bsmr_capi.hip.
 #pragma once
 
-#include "spmm_kernels.hpp"
+#include "spmm_blocked_kernels.hpp"   // (includes spmm_kernels.hpp)
+
+// Device format of bsmr_backward_attach_blocks (csrc/blocked_capi.hpp).  Residue lists: [0] the rows outside panels with
+// blocks (destination = the row of Y), [1] the rows of panels with blocks (destination = their staging row); the chunk
+// slots of both are numbered through.
+struct BwBlocked {
+    bsmr::BlkPanel* panels = nullptr;   // [numPanels]      panels with blocks
+    uint32_t* panelRows = nullptr;      // [16 numPanels]   row of S or kBlkNull
+    bsmr::u32x4* cells = nullptr;       // [64 blocks]      cells[b][lane][s]
+    bsmr::u32x4* cols = nullptr;        // [4 blocks]       cols[b][k][s]
+    float* zeros = nullptr;             // [4]              +0: what an empty cell and a padding column load
+    uint32_t* resCols = nullptr;        // [residue]        s(t) of the residue lists: row by row, ascending CSR index
+    uint32_t* resIdx = nullptr;         // [residue]        e(t)
+    bsmr::BwItem* items[2] = {nullptr, nullptr};
+    bsmr::BwSplit* splits[2] = {nullptr, nullptr};
+    uint32_t numPanels = 0, numItems[2] = {0, 0}, numSplits[2] = {0, 0}, numSlots = 0;
+    bsmr_blocked_stats stats{};
+
+    ~BwBlocked() {
+        for (void* p : {(void*)panels, (void*)panelRows, (void*)cells, (void*)cols, (void*)zeros, (void*)resCols, (void*)resIdx,
+                        (void*)items[0], (void*)items[1], (void*)splits[0], (void*)splits[1]})
+            if (p) (void)hipFree(p);
+    }
+};
 
 struct bsmr_backward {
     int device = 0;
@@ -29,8 +52,10 @@ struct bsmr_backward {
                                       // (DESIGN 11); BSMR_GATHER16_LANES=4 / 8 at create: that layout for every width
     float* work = nullptr;            // chunk partials (+ permuted dP) (+ 16-bit copies of the gathered operands),
     uint64_t workFloats = 0;          // grown on demand
+    BwBlocked* blocked = nullptr;     // bsmr_backward_attach_blocks
 
     ~bsmr_backward() {
+        delete blocked;
         for (void* p : {(void*)rowOffsets, (void*)colIndices, (void*)cscRows, (void*)cscToCsr, (void*)items[0], (void*)items[1],
                         (void*)splits[0], (void*)splits[1], (void*)work})
             if (p) (void)hipFree(p);
@@ -92,7 +117,9 @@ void buildItems(const uint32_t* offsets, uint32_t numDest, const std::vector<uin
 }
 
 uint64_t workFloatsFor(const bsmr_backward* bw, uint32_t K, uint32_t nb, bool withPermute) {
-    const uint64_t slots = std::max(bw->numSlots[0], bw->numSlots[1]);
+    uint64_t slots = std::max(bw->numSlots[0], bw->numSlots[1]);
+    // attached blocks: the residue's chunk partials, then 16 fp32 staging rows per panel with blocks
+    if (bw->blocked) slots = std::max<uint64_t>(slots, (uint64_t)bw->blocked->numSlots + 16ull * bw->blocked->numPanels);
     return (slots * K + (withPermute ? bw->nnz : 0u)) * nb;
 }
 
@@ -168,42 +195,43 @@ int checkBackwardCall(const bsmr_backward* bw, uint32_t K, uint32_t nb) {
     return BSMR_OK;
 }
 
-// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.  xMode says what
-// the rows of X are: fp32 (spmmGather), or fp16 / bf16 (spmmGather16).  y16 (16-bit X only): Yout holds xMode's format
-// too; otherwise fp32.
-int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* Xrows, void* Yout, uint32_t nb, hipStream_t s,
-            int xMode = BSMR_COMPUTE_F32, bool y16 = false) {
+// The work lists of one gather: items / splits as built by buildItems, src = s(t), map = e(t) or NULL for e(t) = t.
+struct GatherLists {
+    const bsmr::BwItem* items;
+    uint32_t numItems;
+    const bsmr::BwSplit* splits;
+    uint32_t numSplits;
+    const uint32_t* src;
+    const uint32_t* map;
+};
+
+// The gather and the reduction of its split destinations over one set of lists.  xMode says what the rows of X are: fp32
+// (spmmGather), or fp16 / bf16 (spmmGather16).  y16 (16-bit X only): Yout holds xMode's format too; otherwise fp32.
+// vB / xB / yB / pB: the batch strides of v, X, Y and the partials, in elements.
+int runGather(const bsmr_backward* bw, const GatherLists& L, uint32_t K, const float* v, const void* Xrows, void* Yout,
+              float* partial, uint64_t vB, uint64_t xB, uint64_t yB, uint64_t pB, uint32_t nb, hipStream_t s, int xMode,
+              bool y16) {
     const bool lowp = xMode != BSMR_COMPUTE_F32;
     float* Y = y16 ? nullptr : static_cast<float*>(Yout);
     uint16_t* Y16 = y16 ? static_cast<uint16_t*>(Yout) : nullptr;
     const float* X = lowp ? nullptr : static_cast<const float*>(Xrows);
     const uint16_t* X16 = lowp ? static_cast<const uint16_t*>(Xrows) : nullptr;
-    const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
-    const uint64_t nnz = bw->nnz;
-    const uint64_t xB = (uint64_t)rowsX * K, yB = (uint64_t)rowsY * K, pB = (uint64_t)bw->numSlots[dir] * K;
-    float* partial = bw->work;
-    const uint32_t* map = dir ? bw->cscToCsr : nullptr;
-    if (dir && bw->permuteV && nnz) {   // dP in CSC order, behind the partials of the workspace
-        float* vT = bw->work + pB * nb;
-        hipLaunchKernelGGL(bsmr::spmmPermute, dim3((bw->nnz + 255u) / 256u, nb), dim3(256), 0, s, bw->cscToCsr, bw->nnz, v, vT);
-        BSMR_HIP(hipGetLastError());
-        v = vT;
-        map = nullptr;
-    }
-    const uint32_t* src = dir ? bw->cscRows : bw->colIndices;
+    const uint64_t nnz = vB;
+    const uint32_t* src = L.src;
+    const uint32_t* map = L.map;
     const uint32_t W = K % 256u == 0 ? 256u : K % 128u == 0 ? 128u : K % 64u == 0 ? 64u : 32u;
     const uint32_t slices = K / W;
-    const uint64_t units = (uint64_t)bw->numItems[dir] * slices;
+    const uint64_t units = (uint64_t)L.numItems * slices;
     const uint32_t VE = lowp ? lanes16For(bw, W) : 0u;
     const uint64_t unitsPerBlock = lowp ? 4u * (64u / (W / VE)) : 4u * (W >= 128u ? 1u : 64u / (W / 4u));
     const dim3 grid((uint32_t)((units + unitsPerBlock - 1) / unitsPerBlock), nb);
     if (units && y16) {
 #define BSMR_SPMM16_OUT_LAUNCH(WW)                                                                                           \
     if (VE == 8u)                                                                                                            \
-        launchGather16Out<WW, 8>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, \
+        launchGather16Out<WW, 8>(map != nullptr, xMode, grid, s, L.items, L.numItems, slices, src, map, v, X16,              \
                                  Y16, partial, K, nnz, xB, yB, pB);                                                          \
     else                                                                                                                     \
-        launchGather16Out<WW, 4>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, \
+        launchGather16Out<WW, 4>(map != nullptr, xMode, grid, s, L.items, L.numItems, slices, src, map, v, X16,              \
                                  Y16, partial, K, nnz, xB, yB, pB)
         switch (W) {
         case 256: BSMR_SPMM16_OUT_LAUNCH(256); break;
@@ -216,10 +244,10 @@ int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* 
     } else if (units && lowp) {
 #define BSMR_SPMM16_LAUNCH(WW)                                                                                               \
     if (VE == 8u)                                                                                                            \
-        launchGather16<WW, 8>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, Y, \
+        launchGather16<WW, 8>(map != nullptr, xMode, grid, s, L.items, L.numItems, slices, src, map, v, X16, Y,              \
                               partial, K, nnz, xB, yB, pB);                                                                  \
     else                                                                                                                     \
-        launchGather16<WW, 4>(map != nullptr, xMode, grid, s, bw->items[dir], bw->numItems[dir], slices, src, map, v, X16, Y, \
+        launchGather16<WW, 4>(map != nullptr, xMode, grid, s, L.items, L.numItems, slices, src, map, v, X16, Y,              \
                               partial, K, nnz, xB, yB, pB)
         switch (W) {
         case 256: BSMR_SPMM16_LAUNCH(256); break;
@@ -231,7 +259,7 @@ int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* 
         BSMR_HIP(hipGetLastError());
     } else if (units) {
 #define BSMR_SPMM_LAUNCH(WW, MAP)                                                                                            \
-    hipLaunchKernelGGL((bsmr::spmmGather<WW, MAP>), grid, dim3(256), 0, s, bw->items[dir], bw->numItems[dir], slices, src, \
+    hipLaunchKernelGGL((bsmr::spmmGather<WW, MAP>), grid, dim3(256), 0, s, L.items, L.numItems, slices, src,                 \
                        map, v, X, Y, partial, K, nnz, xB, yB, pB)
         const bool m = map != nullptr;
         switch (W) {
@@ -243,21 +271,42 @@ int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* 
 #undef BSMR_SPMM_LAUNCH
         BSMR_HIP(hipGetLastError());
     }
-    if (bw->numSplits[dir] && y16) {
-        const uint64_t threads = (uint64_t)bw->numSplits[dir] * (K / 4u);
+    if (L.numSplits && y16) {
+        const uint64_t threads = (uint64_t)L.numSplits * (K / 4u);
         const dim3 rgrid((uint32_t)((threads + 255u) / 256u), nb);
         if (xMode == BSMR_COMPUTE_F16)
-            hipLaunchKernelGGL(bsmr::spmmReduce16<0>, rgrid, dim3(256), 0, s, bw->splits[dir], bw->numSplits[dir], partial, Y16, K, yB, pB);
+            hipLaunchKernelGGL(bsmr::spmmReduce16<0>, rgrid, dim3(256), 0, s, L.splits, L.numSplits, partial, Y16, K, yB, pB);
         else
-            hipLaunchKernelGGL(bsmr::spmmReduce16<1>, rgrid, dim3(256), 0, s, bw->splits[dir], bw->numSplits[dir], partial, Y16, K, yB, pB);
+            hipLaunchKernelGGL(bsmr::spmmReduce16<1>, rgrid, dim3(256), 0, s, L.splits, L.numSplits, partial, Y16, K, yB, pB);
         BSMR_HIP(hipGetLastError());
-    } else if (bw->numSplits[dir]) {
-        const uint64_t threads = (uint64_t)bw->numSplits[dir] * (K / 4u);
-        hipLaunchKernelGGL(bsmr::spmmReduce, dim3((uint32_t)((threads + 255u) / 256u), nb), dim3(256), 0, s, bw->splits[dir],
-                           bw->numSplits[dir], partial, Y, K, yB, pB);
+    } else if (L.numSplits) {
+        const uint64_t threads = (uint64_t)L.numSplits * (K / 4u);
+        hipLaunchKernelGGL(bsmr::spmmReduce, dim3((uint32_t)((threads + 255u) / 256u), nb), dim3(256), 0, s, L.splits,
+                           L.numSplits, partial, Y, K, yB, pB);
         BSMR_HIP(hipGetLastError());
     }
     return BSMR_OK;
+}
+
+// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.  xMode / y16 as
+// runGather.
+int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* Xrows, void* Yout, uint32_t nb, hipStream_t s,
+            int xMode = BSMR_COMPUTE_F32, bool y16 = false) {
+    const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
+    const uint64_t nnz = bw->nnz;
+    const uint64_t xB = (uint64_t)rowsX * K, yB = (uint64_t)rowsY * K, pB = (uint64_t)bw->numSlots[dir] * K;
+    float* partial = bw->work;
+    const uint32_t* map = dir ? bw->cscToCsr : nullptr;
+    if (dir && bw->permuteV && nnz) {   // dP in CSC order, behind the partials of the workspace
+        float* vT = bw->work + pB * nb;
+        hipLaunchKernelGGL(bsmr::spmmPermute, dim3((bw->nnz + 255u) / 256u, nb), dim3(256), 0, s, bw->cscToCsr, bw->nnz, v, vT);
+        BSMR_HIP(hipGetLastError());
+        v = vT;
+        map = nullptr;
+    }
+    const GatherLists L{bw->items[dir], bw->numItems[dir], bw->splits[dir], bw->numSplits[dir],
+                        dir ? bw->cscRows : bw->colIndices, map};
+    return runGather(bw, L, K, v, Xrows, Yout, partial, nnz, xB, yB, pB, nb, s, xMode, y16);
 }
 
 }  // namespace

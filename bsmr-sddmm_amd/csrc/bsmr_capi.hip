@@ -3751,5 +3751,6 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
 #include "sharded_capi.hpp"
 #include "colreorder_capi.hpp"
 #include "backward_capi.hpp"
+#include "blocked_capi.hpp"
 #include "softmax_capi.hpp"
 #include "attention_capi.hpp"

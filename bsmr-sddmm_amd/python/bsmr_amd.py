@@ -126,6 +126,14 @@ class BackwardStats(C.Structure):
                 ("workspace_bytes", C.c_uint64)]
 
 
+class BlockedStats(C.Structure):
+    """bsmr_blocked_stats: what bsmr_blocked_check counts in an RPHM (device_index_bytes: attached handles only)"""
+    _fields_ = [("panels", C.c_uint32), ("panels_with_blocks", C.c_uint32), ("blocks", C.c_uint64),
+                ("block_entries", C.c_uint64), ("padding_columns", C.c_uint64), ("residue_entries", C.c_uint64),
+                ("max_residue_row", C.c_uint32), ("split_residue_rows", C.c_uint32), ("max_blocks_per_panel", C.c_uint32),
+                ("residue_items", C.c_uint32), ("device_index_bytes", C.c_uint64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("convert_ms", C.c_float), ("dense_ms", C.c_float),
                 ("sparse_ms", C.c_float)]
@@ -220,6 +228,13 @@ HIP_SYMBOLS = {
                                C.c_void_p]),
     "bsmr_sddmm_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_blocked_check": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RphmDesc),
+                                     C.POINTER(BlockedStats), C.c_size_t]),
+    "bsmr_backward_attach_blocks": (C.c_int, [C.c_void_p, C.POINTER(RphmDesc)]),
+    "bsmr_backward_get_blocked_stats": (C.c_int, [C.c_void_p, C.POINTER(BlockedStats), C.c_size_t]),
+    "bsmr_spmm_blocked": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bsmr_spmm_blocked_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                       C.c_void_p]),
     "bsmr_sparse_softmax": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsmr_sparse_softmax_backward": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                C.c_void_p]),
@@ -658,10 +673,8 @@ def plan_options(**changes) -> PlanOptions:
     return o
 
 
-def plan_from_arrays(M, N, nnz, arrays: dict, device=0, options: PlanOptions = None):
-    """bsmr_plan_create straight from RPHM-layout numpy arrays (what a reference
-    maintainer would pass from RPHM's host vectors).  Returns the plan handle.
-    options: a PlanOptions -> bsmr_plan_create_ex (the environment is then not consulted)."""
+def rphm_desc(M, N, nnz, arrays: dict):
+    """bsmr_rphm_desc over RPHM-layout numpy arrays: (desc, the contiguous arrays it points into - keep them alive)"""
     keep = {k: np.ascontiguousarray(arrays[k], dtype=np.uint32) for k in
             ("reorderedRows", "denseCols", "blockOffsets", "blockValues", "sparseValueOffsets",
              "sparseValues", "sparseRelativeRows", "sparseColIndices")}
@@ -678,6 +691,14 @@ def plan_from_arrays(M, N, nnz, arrays: dict, device=0, options: PlanOptions = N
     d.sparse_values = cast(keep["sparseValues"])
     d.sparse_relative_rows = cast(keep["sparseRelativeRows"])
     d.sparse_col_indices = cast(keep["sparseColIndices"])
+    return d, keep
+
+
+def plan_from_arrays(M, N, nnz, arrays: dict, device=0, options: PlanOptions = None):
+    """bsmr_plan_create straight from RPHM-layout numpy arrays (what a reference
+    maintainer would pass from RPHM's host vectors).  Returns the plan handle.
+    options: a PlanOptions -> bsmr_plan_create_ex (the environment is then not consulted)."""
+    d, keep = rphm_desc(M, N, nnz, arrays)
     out = C.c_void_p()
     if options is not None:
         st = hip().bsmr_plan_create_ex(C.byref(out), device, C.byref(d), C.byref(options))
@@ -787,6 +808,45 @@ def sddmm_backward_16(bw, K: int, dP_ptr: int, A16_ptr: int, B16_ptr: int, dA16_
     """dA16 = round(S_dP widen(B16)), dB16 = round(S_dP^T widen(A16)); dA16_ptr / dB16_ptr None (or 0) skips that product"""
     _check(hip().bsmr_sddmm_backward_16(bw, K, dP_ptr or None, A16_ptr or None, B16_ptr or None, dA16_ptr or None,
                                         dB16_ptr or None, num_batches, mode, stream), "bsmr_sddmm_backward_16")
+
+
+# --- blocked SpMM: Y = S_v X over the RPHM's dense blocks (fp32 MFMA) + the gather over the residue ---
+def blocked_check_status(rows, cols, row_offsets, col_indices, arrays: dict):
+    """bsmr_blocked_check (host only): (status, statistics as a dict) of RPHM-layout arrays against a CSR"""
+    ro = np.ascontiguousarray(row_offsets, dtype=np.uint32)
+    ci = np.ascontiguousarray(col_indices, dtype=np.uint32)
+    d, keep = rphm_desc(rows, cols, int(ci.size), arrays)
+    s = BlockedStats()
+    st = hip().bsmr_blocked_check(rows, cols, ci.size, _ptr(ro), _ptr(ci) if ci.size else None, C.byref(d), C.byref(s),
+                                  C.sizeof(s))
+    return st, {k: getattr(s, k) for k, _ in BlockedStats._fields_}
+
+
+def backward_attach_blocks_status(bw, rows, cols, nnz, arrays: dict) -> int:
+    d, keep = rphm_desc(rows, cols, nnz, arrays)
+    return hip().bsmr_backward_attach_blocks(bw, C.byref(d))
+
+
+def backward_attach_blocks(bw, rows, cols, nnz, arrays: dict):
+    """bsmr_backward_attach_blocks: the handle serves spmm_blocked afterwards (arrays: Pipeline.arrays())"""
+    _check(backward_attach_blocks_status(bw, rows, cols, nnz, arrays), "bsmr_backward_attach_blocks")
+
+
+def backward_blocked_stats(bw) -> dict:
+    s = BlockedStats()
+    _check(hip().bsmr_backward_get_blocked_stats(bw, C.byref(s), C.sizeof(s)), "bsmr_backward_get_blocked_stats")
+    return {k: getattr(s, k) for k, _ in BlockedStats._fields_}
+
+
+def spmm_blocked(bw, K: int, v_ptr: int, X_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0, mode=COMPUTE_F32):
+    """Y = S_v X on a handle with attached blocks; mode F16 / BF16: X and Y are 16-bit rows of that format
+    (bsmr_spmm_blocked_16)"""
+    if mode == COMPUTE_F32:
+        _check(hip().bsmr_spmm_blocked(bw, K, v_ptr or None, X_ptr or None, Y_ptr or None, num_batches, stream),
+               "bsmr_spmm_blocked")
+    else:
+        _check(hip().bsmr_spmm_blocked_16(bw, K, v_ptr or None, X_ptr or None, Y_ptr or None, num_batches, mode, stream),
+               "bsmr_spmm_blocked_16")
 
 
 def sparse_softmax(bw, scale: float, X_ptr: int, Y_ptr: int, num_batches: int = 1, stream: int = 0):

@@ -26,6 +26,14 @@ bsmr_sparse_softmax_backward, bsmr_sparse_attention_backward), attention by comp
 so SDDMM -> softmax -> SpMM, the usual sparse-attention layer, trains on the engine end to end.  attention(fused=True)
 takes the fused path; the default (fused=False) is the composition, unchanged.
 
+blocked (default False: every result bit for bit as without the argument): with blocked=True the operator attaches the
+pipeline's RPHM to its backward handle (bsmr_backward_attach_blocks) and the row direction - spmm(transpose=False), hence
+attention's last step, and the dA of sddmm's backward - runs bsmr_spmm_blocked[_16]: the entries in the RPHM's dense 16 x 16
+blocks on the fp32 MFMA, one read of a row of X per block instead of one per entry, the rest on the gather.  Same
+function, another summation order (include/bsmr_hip.h "Blocked SpMM": the result depends on the reordering; an empty block
+cell meets a non-finite X as 0 * x).  The transposed spmm, dB, softmax, softmax_spmm and every SDDMM are untouched.
+blocked=True needs gather_mode=COMPUTE_F32 (ValueError otherwise).
+
 gather_mode (default COMPUTE_F32: every result bit for bit as without the argument) is the format in which the gathers
 read their operand rows: with COMPUTE_F16 / COMPUTE_BF16 spmm's X, the dY of its dX, and the B / A of sddmm's dA / dB are
 rounded once per call and gathered as 16-bit rows (half the bytes); values, sums and results stay fp32.  spmm then
@@ -61,9 +69,13 @@ _MODE16 = {torch.float16: eng.COMPUTE_F16, torch.bfloat16: eng.COMPUTE_BF16}   #
 
 
 class SparseOperator:
-    def __init__(self, csr: "eng.CSR", alpha=0.3, delta=0.3, mode=eng.COMPUTE_F16, device=0, gather_mode=eng.COMPUTE_F32):
+    def __init__(self, csr: "eng.CSR", alpha=0.3, delta=0.3, mode=eng.COMPUTE_F16, device=0, gather_mode=eng.COMPUTE_F32,
+                 blocked=False):
         if gather_mode not in (eng.COMPUTE_F16, eng.COMPUTE_BF16, eng.COMPUTE_F32):
             raise ValueError(f"gather_mode: {gather_mode!r} is not one of COMPUTE_F16, COMPUTE_BF16, COMPUTE_F32")
+        if blocked and gather_mode != eng.COMPUTE_F32:
+            raise ValueError("blocked=True needs gather_mode=COMPUTE_F32: the blocked SpMM has no rounding-pass form")
+        self.blocked = bool(blocked)
         self.csr = csr
         self.M, self.N, self.nnz = csr.rows, csr.cols, csr.nnz
         self.mode = mode
@@ -76,6 +88,8 @@ class SparseOperator:
         self._plan = plan
         self._bw = eng.backward_create(self.M, self.N, csr.row_offsets, csr.col_indices,
                                        row_order=self.pipeline.array("reorderedRows"), device=device)
+        if self.blocked:
+            eng.backward_attach_blocks(self._bw, self.M, self.N, self.nnz, self.pipeline.arrays())
 
     def __del__(self):
         if getattr(self, "_bw", None):
@@ -187,6 +201,10 @@ class SparseOperator:
         b, K = self._check(X, "X", rows_x, None)
         self._check_values(v, b)
         Y = torch.empty((rows_y, K) if b is None else (b, rows_y, K), dtype=X.dtype, device=self.device)
+        if self.blocked and not transpose:
+            eng.spmm_blocked(self._bw, K, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
+                             mode=_MODE16.get(X.dtype, eng.COMPUTE_F32))
+            return Y
         if X.dtype in _MODE16:
             eng.spmm_16(self._bw, K, transpose, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
                         mode=_MODE16[X.dtype])
@@ -262,6 +280,12 @@ class SparseOperator:
         mode16 = self._mode16(A, B, "A and B")
         dA = torch.empty_like(A) if need_a else None
         dB = torch.empty_like(B) if need_b else None
+        if self.blocked and need_a:   # dA = S_dP B over the blocks; dB (the column direction) stays on the gather
+            eng.spmm_blocked(self._bw, K, dP.data_ptr(), B.data_ptr(), dA.data_ptr(), b or 1, self._stream(),
+                             mode=eng.COMPUTE_F32 if mode16 is None else mode16)
+            need_a = False
+            if not need_b:
+                return dA, dB
         if mode16 is not None:
             eng.sddmm_backward_16(self._bw, K, dP.data_ptr(), A.data_ptr(), B.data_ptr(), dA.data_ptr() if need_a else None,
                                   dB.data_ptr() if need_b else None, b or 1, self._stream(), mode=mode16)

@@ -43,6 +43,8 @@
  *                           fp16 / bf16 tensors only - 16-bit operands in, 16-bit Y / dA / dB out, the values stay fp32
  *   bsmr_sparse_softmax / bsmr_sparse_softmax_backward
  *                        <- no reference counterpart: the row softmax over S's pattern and its gradient
+ *   bsmr_blocked_check / bsmr_backward_attach_blocks / bsmr_spmm_blocked / bsmr_spmm_blocked_16
+ *                        <- no reference counterpart: Y = S_v X over the RPHM's dense 16 x 16 blocks on the fp32 MFMA
  *   bsmr_mem_info        <- cudaMemGetInfo in calculateBlockSize (src/rowReordering.cu:1010-1013)
  *   bsmr_dev_alloc / bsmr_dev_free / bsmr_memcpy_h2d / bsmr_memcpy_d2h / bsmr_dev_memset
  *                        <- dev::vector<T> ctor/dtor and h2d()/d2h() (include/devVector.cuh:54-126,
@@ -447,12 +449,14 @@ int bsmr_plan_reserve(bsmr_plan *plan, uint32_t K);
  *   16 bytes  the operand matrices and their 16-bit copies: A_dev, B_dev (fp32, bsmr_sddmm, _batch, _timed, _lowp,
  *             bsmr_plan_tune, bsmr_convert_operands, bsmr_sddmm_backward[_mode]), A16_dev, B16_dev (bsmr_convert_operands,
  *             bsmr_sddmm_lowp, bsmr_sddmm_16, bsmr_sddmm_backward_16), X_dev, Y_dev (bsmr_spmm[_mode]), X16_dev, Y_dev
- *             (bsmr_spmm_lowp), X16_dev, Y16_dev (bsmr_spmm_16), dA_dev, dB_dev (bsmr_sddmm_backward[_mode]), dA16_dev,
+ *             (bsmr_spmm_lowp), X16_dev, Y16_dev (bsmr_spmm_16, bsmr_spmm_blocked_16), X_dev, Y_dev (bsmr_spmm_blocked),
+ *             dA_dev, dB_dev (bsmr_sddmm_backward[_mode]), dA16_dev,
  *             dB16_dev (bsmr_sddmm_backward_16).  The kernels move them 16 bytes at a time (global_load_dwordx4, LDS-DMA of
  *             16 bytes per lane, 16-byte stores of the conversion pass, float4 and 8 x 16-bit loads and stores in the
  *             backward); K is a multiple of 32, so every row, column and batch then starts on 16 bytes.
  *    4 bytes  the value arrays, read and written one float at a time: P_dev (all of the above), v_dev (bsmr_spmm[_mode],
- *             bsmr_spmm_lowp, bsmr_spmm_16), dP_dev (bsmr_sddmm_backward[_mode], bsmr_sddmm_backward_16), X_dev / Y_dev /
+ *             bsmr_spmm_lowp, bsmr_spmm_16, bsmr_spmm_blocked[_16]), dP_dev (bsmr_sddmm_backward[_mode],
+ *             bsmr_sddmm_backward_16), X_dev / Y_dev /
  *             dY_dev / dX_dev of bsmr_sparse_softmax[_backward], and
  *             in_dev / out_dev of bsmr_batched_transpose.  A batch with an odd nnz puts its second problem on an odd
  *             float; that is within the contract.
@@ -733,6 +737,91 @@ int bsmr_sparse_attention_backward_16(bsmr_backward *bw, uint32_t Kv, float scal
                                       const float *m_dev, const float *s_dev, const float *dW_dev, const void *O16_dev,
                                       const void *dO16_dev, float *dP_dev, float *W_dev, uint32_t num_batches,
                                       int compute_mode, void *stream);
+
+/* ---- Blocked SpMM: Y = S_v X over the RPHM's dense 16 x 16 blocks (revision 5, added without any layout change) ----
+ * The row direction of bsmr_spmm with the dense part of the reordering put to use: in a row panel the 16 columns of a
+ * dense block are shared by 16 output rows, so a row of X is read once per block instead of once per stored entry and the
+ * block is multiplied on v_mfma_f32_16x16x4_f32.  Opt-in: a handle serves these calls after
+ * bsmr_backward_attach_blocks; every other call on it is unchanged.  Only Y = S_v X (the rows of S as destinations); the
+ * column direction (transpose = 1, dB, dX) stays on the gather.
+ *
+ * Numerical contract.  Row r is row i of panel p (r = reordered_rows[16 p + i]), the panel's blocks are b0 .. b(nb-1) in
+ * block_offsets order.
+ *   Block chain  B[r,k]: one sequential fp32 fmaf chain from +0 over the blocks in order and, inside a block, over the
+ *                column positions j = 0 .. 15 in order: acc = fmaf(a_ij, x_j[k], acc), with a_ij = v[t] where
+ *                block_values[b][i][j] = t is a CSR index and +0 where the cell is empty (0xFFFFFFFF); x_j is row
+ *                dense_cols[16 b + j] of X and, for a padding column (id N), a row of +0 that is never loaded.  This is
+ *                what the instruction computes when MFMA s of a block takes the positions 4 s .. 4 s + 3: a k-ordered fmaf
+ *                chain with one rounding per product (the exact-fp32 forward kernel is pinned to the same fact,
+ *                oracle_dense_f32_twin).
+ *   Residue      R[r,k]: the gather contract of "SDDMM backward" applied to the row's residue entries in ascending CSR
+ *                index - one chain from +0, a list longer than BSMR_BACKWARD_CHUNK cut into chunks, the partials added in
+ *                chunk order.
+ *   Result       Y[r,k] = fl(B[r,k] + R[r,k]), one fp32 addition, for the rows of panels that have at least one block;
+ *                Y[r,:] = R[r,:], the same bits, for the rows of panels without blocks; rows in no panel (empty rows)
+ *                are exactly +0.
+ * No atomics: every element has one writer, results are bitwise reproducible call to call, stream to stream and batch to
+ * batch.  They depend on the attached RPHM (its block order and its dense / residue split), so unlike bsmr_spmm they are
+ * NOT independent of the reordering: another row_order, alpha or delta gives another summation order.
+ * Empty cells - the one semantic difference from bsmr_spmm: an empty cell multiplies +0 by a value of X that the gather
+ * never reads for that row.  With finite X this changes nothing (fmaf(0, x, acc) = acc, apart from -0 -> +0).  If X[c,k]
+ * is +-inf or NaN, every row of every panel that holds c as a block column but does not store (r, c) gets NaN in feature
+ * k, where the gather leaves that row alone; rows that store c behave as in the gather.
+ * Error bound:  |Y - Y64| <= (max(16 nb, n_r) + 4) u sum|v||x|,  u = 2^-24, n_r the row's residue count (each term passes
+ * at most 16 nb roundings of the block chain or n_r + 1 of the residue, then one more addition; two units cover second
+ * order), plus the subnormal term of DESIGN.md 10 where products underflow.
+ * 16-bit form (bsmr_spmm_blocked_16): X is fp16 / bf16 rows, widened exactly; the contract above applies to the widened
+ * values; Y16 = round(Y) is applied once, after the final addition (B and R are added in fp32), with the casts of
+ * bsmr_spmm_16.
+ *
+ * bsmr_blocked_check: host only, no device, like bsmr_csr_transpose - whether `desc` is a partition of the CSR into block
+ * cells and residue entries, and its statistics.  BSMR_ERR_INVALID_ARG: a NULL argument, a CSR that bsmr_backward_create
+ * would refuse, desc->M / N / nnz different from M / N / nnz.  BSMR_ERR_BAD_PLAN: a CSR index missing from, or listed twice
+ * across, block_values and sparse_values; a block cell whose entry's row is not reordered_rows[16 p + i] or whose column
+ * is not dense_cols[16 b + j]; a non-empty cell in a padding column; a column id above N; a residue entry whose (relative
+ * row, column) disagrees with the CSR; a non-monotone offset array (or one that does not start at 0); a duplicate or
+ * out-of-range reordered_rows; num_row_panels other than ceil(num_nonzero_rows / 16).  Otherwise the statistics are
+ * written, at most out_size bytes of them (the struct only grows at its end).
+ *
+ * bsmr_backward_attach_blocks: runs the same check against the handle's CSR before any device call, then builds and uploads
+ * the device format: per block 64 bytes of column ids and 1 KiB of cells (CSR index or null) in the lane order of the
+ * kernel, per panel with blocks its rows, and the residue as per-row gather lists (every row of S has one, in ascending
+ * CSR index, chunked by BSMR_BACKWARD_CHUNK; rows of panels without blocks write Y, rows of panels with blocks an fp32
+ * staging row).  A second attach on one handle is BSMR_ERR_INVALID_ARG.  bsmr_backward_get_blocked_stats: the statistics
+ * of the attached desc with device_index_bytes filled in; BSMR_ERR_BAD_PLAN without attached blocks.
+ * Workspace: chunk partials of the residue and the staging rows, 16 K floats per panel with blocks and batch.  On a handle
+ * with attached blocks bsmr_backward_reserve(K, num_batches) covers them (the layout of every other call is unchanged:
+ * chunk partials first); after it the blocked calls allocate nothing and can be captured in a graph.
+ *
+ * bsmr_spmm_blocked / bsmr_spmm_blocked_16 follow the argument rules of bsmr_spmm / bsmr_spmm_16 (transpose 0), checked
+ * before any device work: a NULL handle is BSMR_ERR_INVALID_ARG, K = 0 or not a multiple of 32 BSMR_ERR_UNSUPPORTED_K, more
+ * than 65535 batches or a compute_mode other than BSMR_COMPUTE_F16 / _BF16 BSMR_ERR_INVALID_ARG, a handle without attached
+ * blocks BSMR_ERR_BAD_PLAN, then the pointers (16 bytes for X and Y, 4 for v).  num_batches = 0 is a no-op; with nnz = 0 v
+ * and X may be NULL and Y is all zeros.  Nothing is read outside v and X or written outside Y (M K, N K, nnz elements, times
+ * num_batches); all addresses are formed in 64 bits.  A panel is one wave's serial loop over its blocks (no panel
+ * splitting): max_blocks_per_panel says how long the longest is. */
+typedef struct bsmr_blocked_stats {
+    uint32_t panels;               /* row panels of the desc                                                  */
+    uint32_t panels_with_blocks;
+    uint64_t blocks;               /* dense 16 x 16 blocks                                                    */
+    uint64_t block_entries;        /* stored entries in block cells: fill = block_entries / (256 blocks)      */
+    uint64_t padding_columns;      /* block columns with the id N                                             */
+    uint64_t residue_entries;
+    uint32_t max_residue_row;      /* most residue entries of one row                                         */
+    uint32_t split_residue_rows;   /* rows whose residue is longer than BSMR_BACKWARD_CHUNK                   */
+    uint32_t max_blocks_per_panel;
+    uint32_t residue_items;        /* work items of the residue gather: one per row of S (a row without residue
+                                      zeroes its destination), one per chunk of a split row                   */
+    uint64_t device_index_bytes;   /* bsmr_backward_get_blocked_stats: the arrays attach uploaded; 0 from bsmr_blocked_check */
+} bsmr_blocked_stats;
+int bsmr_blocked_check(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t *row_offsets, const uint32_t *col_indices,
+                       const bsmr_rphm_desc *desc, bsmr_blocked_stats *out, size_t out_size);
+int bsmr_backward_attach_blocks(bsmr_backward *bw, const bsmr_rphm_desc *desc);
+int bsmr_backward_get_blocked_stats(const bsmr_backward *bw, bsmr_blocked_stats *out, size_t out_size);
+int bsmr_spmm_blocked(bsmr_backward *bw, uint32_t K, const float *v_dev, const float *X_dev, float *Y_dev,
+                      uint32_t num_batches, void *stream);
+int bsmr_spmm_blocked_16(bsmr_backward *bw, uint32_t K, const float *v_dev, const void *X16_dev, void *Y16_dev,
+                         uint32_t num_batches, int compute_mode, void *stream);
 
 /* Host operands in, host P out (upload, `iters` timed repetitions after one
  * warm-up, download).  ms_per_iter may be NULL. */
