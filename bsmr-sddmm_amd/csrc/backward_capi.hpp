@@ -14,7 +14,7 @@
 
 // Device format of bsmr_backward_attach_blocks (csrc/blocked_capi.hpp).  Residue lists: [0] the rows outside panels with
 // blocks (destination = the row of Y), [1] the rows of panels with blocks (destination = their staging row); the chunk
-// slots of both are numbered through.
+// slots of both are numbered through.  segs / splitPanels exist only on a handle attached with segment_blocks >= 1.
 struct BwBlocked {
     bsmr::BlkPanel* panels = nullptr;   // [numPanels]      panels with blocks
     uint32_t* panelRows = nullptr;      // [16 numPanels]   row of S or kBlkNull
@@ -25,12 +25,15 @@ struct BwBlocked {
     uint32_t* resIdx = nullptr;         // [residue]        e(t)
     bsmr::BwItem* items[2] = {nullptr, nullptr};
     bsmr::BwSplit* splits[2] = {nullptr, nullptr};
+    bsmr::BlkSegment* segs = nullptr;       // [numSegs]        segment_blocks >= 1: the work units, panel by panel
+    bsmr::BlkSplit* splitPanels = nullptr;  // [numSplitPanels] the panels cut into two or more segments
     uint32_t numPanels = 0, numItems[2] = {0, 0}, numSplits[2] = {0, 0}, numSlots = 0;
+    uint32_t segmentBlocks = 0, numSegs = 0, numSplitPanels = 0, numPartials = 0;   // numPartials: segments of split panels
     bsmr_blocked_stats stats{};
 
     ~BwBlocked() {
         for (void* p : {(void*)panels, (void*)panelRows, (void*)cells, (void*)cols, (void*)zeros, (void*)resCols, (void*)resIdx,
-                        (void*)items[0], (void*)items[1], (void*)splits[0], (void*)splits[1]})
+                        (void*)items[0], (void*)items[1], (void*)splits[0], (void*)splits[1], (void*)segs, (void*)splitPanels})
             if (p) (void)hipFree(p);
     }
 };
@@ -118,8 +121,11 @@ void buildItems(const uint32_t* offsets, uint32_t numDest, const std::vector<uin
 
 uint64_t workFloatsFor(const bsmr_backward* bw, uint32_t K, uint32_t nb, bool withPermute) {
     uint64_t slots = std::max(bw->numSlots[0], bw->numSlots[1]);
-    // attached blocks: the residue's chunk partials, then 16 fp32 staging rows per panel with blocks
-    if (bw->blocked) slots = std::max<uint64_t>(slots, (uint64_t)bw->blocked->numSlots + 16ull * bw->blocked->numPanels);
+    // attached blocks: the residue's chunk partials, then 16 fp32 staging rows per panel with blocks, then 16 fp32
+    // partial rows per segment of a split panel
+    if (bw->blocked)
+        slots = std::max<uint64_t>(slots, (uint64_t)bw->blocked->numSlots + 16ull * bw->blocked->numPanels +
+                                              16ull * bw->blocked->numPartials);
     return (slots * K + (withPermute ? bw->nnz : 0u)) * nb;
 }
 

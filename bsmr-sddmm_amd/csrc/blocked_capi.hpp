@@ -9,8 +9,11 @@
 //     index.  Every row of S gets a list (an empty one zeroes its destination), cut into chunks of BSMR_BACKWARD_CHUNK
 //     exactly as buildItems cuts the rows; rows are scheduled in reordered_rows order, then the empty rows;
 //   * cells and columns are transposed into the lane order of the kernel.
+//   * segment_blocks = S >= 1: every panel's block list is cut into ceil(nb / S) segments; a panel of one segment keeps
+//     the finish of the panel form, the segments of a split panel get consecutive slots of the partial area.
 // Workspace of a call (K, b), in floats: [b][numSlots][K] chunk partials of the residue, then [b][16 numPanels][K]
-// staging rows (workFloatsFor covers both on a handle with attached blocks).
+// staging rows, then [b][16 numPartials][K] segment partials (workFloatsFor covers all three on a handle with attached
+// blocks).
 // Included at the end of bsmr_capi.hip, after backward_capi.hpp.
 #pragma once
 
@@ -22,8 +25,11 @@ struct BlockedHost {
     std::vector<uint32_t> resOffsets; // [M + 1] residue entries before each row
 };
 
+// segments of a panel of nb >= 1 blocks
+uint64_t segmentsOf(uint32_t nb, uint32_t S) { return S ? ((uint64_t)nb + S - 1u) / S : 1u; }
+
 int blockedCheck(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* ro, const uint32_t* ci, const bsmr_rphm_desc* d,
-                 BlockedHost& h) {
+                 uint32_t S, BlockedHost& h) {
     if (!d) return BSMR_ERR_INVALID_ARG;
     if (int st = checkCsr(M, N, nnz, ro, ci)) return st;
     if (d->M != M || d->N != N || d->nnz != nnz) return BSMR_ERR_INVALID_ARG;
@@ -51,6 +57,8 @@ int blockedCheck(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* ro, const
     s.panels = P;
     s.blocks = blocks;
     s.residue_entries = residue;
+    s.segment_blocks = S;
+    uint64_t segments = 0;
     h.inBlock.assign(nnz, 0);
     std::vector<uint8_t> seen(nnz, 0);
     // entry t must be stored at (row, col) of the CSR, once
@@ -66,6 +74,8 @@ int blockedCheck(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* ro, const
         const uint32_t nb = bo[p + 1] - bo[p];
         s.panels_with_blocks += nb ? 1u : 0u;
         s.max_blocks_per_panel = std::max(s.max_blocks_per_panel, nb);
+        s.split_panels += S && nb > S ? 1u : 0u;
+        segments += nb ? segmentsOf(nb, S) : 0u;
         for (uint64_t b = bo[p]; b < bo[p + 1]; ++b) {
             const uint32_t* cols = d->dense_cols + 16u * b;
             for (uint32_t j = 0; j < 16; ++j) {
@@ -89,6 +99,8 @@ int blockedCheck(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* ro, const
         claimed = s.block_entries + so[p + 1];
     }
     if (claimed != nnz) return BSMR_ERR_BAD_PLAN;   // every claim was a different entry: equal counts = a partition
+    s.segments = (uint32_t)segments;                // at most one per block: blocks < 2^32
+    s.max_blocks_per_segment = S ? std::min(S, s.max_blocks_per_panel) : s.max_blocks_per_panel;
     constexpr uint32_t C = BSMR_BACKWARD_CHUNK;
     h.resOffsets.assign((size_t)M + 1u, 0u);
     for (uint32_t r = 0; r < M; ++r) {
@@ -116,9 +128,10 @@ int runBlocked(bsmr_backward* bw, uint32_t K, const float* v, const void* X, voi
     const bool y16 = mode != BSMR_COMPUTE_F32;
     const uint64_t nnz = bw->nnz;
     const uint64_t xB = (uint64_t)bw->N * K, yB = (uint64_t)bw->M * K, pB = (uint64_t)f.numSlots * K;
-    const uint64_t rB = 16ull * f.numPanels * K;
+    const uint64_t rB = 16ull * f.numPanels * K, sB = 16ull * f.numPartials * K;
     float* partial = bw->work;
     float* stage = bw->work + pB * nb;
+    float* segPartial = stage + rB * nb;
     // R of the rows outside panels with blocks is their row of Y; R of the others waits in fp32 for the block chain
     const GatherLists toY{f.items[0], f.numItems[0], f.splits[0], f.numSplits[0], f.resCols, f.resIdx};
     const GatherLists toStage{f.items[1], f.numItems[1], f.splits[1], f.numSplits[1], f.resCols, f.resIdx};
@@ -126,15 +139,36 @@ int runBlocked(bsmr_backward* bw, uint32_t K, const float* v, const void* X, voi
     if (int st = runGather(bw, toStage, K, v, X, stage, partial, nnz, xB, rB, pB, nb, s, mode, false)) return st;
     if (!f.numPanels) return BSMR_OK;
     const uint32_t groups = (K + 63u) / 64u;
-    const uint64_t units = (uint64_t)f.numPanels * groups;
-    const dim3 grid((uint32_t)((units + 3u) / 4u), nb);
-    auto launch = [&](auto kernel, auto* x, auto* y) {
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, f.panels, f.numPanels, groups, f.panelRows, f.cells, f.cols, f.zeros, v,
-                           x, stage, y, bw->N, K, nnz, xB, yB, rB);
+    if (!f.segmentBlocks) {   // the panel form
+        const uint64_t units = (uint64_t)f.numPanels * groups;
+        const dim3 grid((uint32_t)((units + 3u) / 4u), nb);
+        auto launch = [&](auto kernel, auto* x, auto* y) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, f.panels, f.numPanels, groups, f.panelRows, f.cells, f.cols,
+                               f.zeros, v, x, stage, y, bw->N, K, nnz, xB, yB, rB);
+        };
+        if (mode == BSMR_COMPUTE_F32) launch(bsmr::spmmBlocks, static_cast<const float*>(X), static_cast<float*>(Y));
+        else if (mode == BSMR_COMPUTE_F16) launch(bsmr::spmmBlocks16<0>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
+        else launch(bsmr::spmmBlocks16<1>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
+        BSMR_HIP(hipGetLastError());
+        return BSMR_OK;
+    }
+    // the segment form; the finishing kernel only where a panel is split
+    const uint64_t units = (uint64_t)f.numSegs * groups;
+    const uint64_t finThreads = 16ull * f.numSplitPanels * (K / 4u);
+    const dim3 grid((uint32_t)((units + 3u) / 4u), nb), finGrid((uint32_t)((finThreads + 255u) / 256u), nb);
+    auto launch = [&](auto kernel, auto finish, auto* x, auto* y) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, f.segs, f.numSegs, groups, f.panelRows, f.cells, f.cols, f.zeros, v,
+                           x, stage, y, bw->N, K, nnz, xB, yB, rB, segPartial, sB);
+        if (f.numSplitPanels)
+            hipLaunchKernelGGL(finish, finGrid, dim3(256), 0, s, f.splitPanels, f.numSplitPanels, f.panelRows, segPartial,
+                               stage, y, K, sB, rB, yB);
     };
-    if (mode == BSMR_COMPUTE_F32) launch(bsmr::spmmBlocks, static_cast<const float*>(X), static_cast<float*>(Y));
-    else if (mode == BSMR_COMPUTE_F16) launch(bsmr::spmmBlocks16<0>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
-    else launch(bsmr::spmmBlocks16<1>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
+    if (mode == BSMR_COMPUTE_F32)
+        launch(bsmr::spmmBlocksSeg, bsmr::spmmBlocksFinish, static_cast<const float*>(X), static_cast<float*>(Y));
+    else if (mode == BSMR_COMPUTE_F16)
+        launch(bsmr::spmmBlocksSeg16<0>, bsmr::spmmBlocksFinish16<0>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
+    else
+        launch(bsmr::spmmBlocksSeg16<1>, bsmr::spmmBlocksFinish16<1>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
     BSMR_HIP(hipGetLastError());
     return BSMR_OK;
 }
@@ -143,12 +177,12 @@ int runBlocked(bsmr_backward* bw, uint32_t K, const float* v, const void* X, voi
 
 extern "C" {
 
-int bsmr_blocked_check(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* row_offsets, const uint32_t* col_indices,
-                       const bsmr_rphm_desc* desc, bsmr_blocked_stats* out, size_t out_size) {
+int bsmr_blocked_check_split(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* row_offsets, const uint32_t* col_indices,
+                             const bsmr_rphm_desc* desc, uint32_t segment_blocks, bsmr_blocked_stats* out, size_t out_size) {
     if (!out) return BSMR_ERR_INVALID_ARG;
     try {
         BlockedHost h;
-        if (int st = blockedCheck(M, N, nnz, row_offsets, col_indices, desc, h)) return st;
+        if (int st = blockedCheck(M, N, nnz, row_offsets, col_indices, desc, segment_blocks, h)) return st;
         memcpy(out, &h.stats, std::min(out_size, sizeof(h.stats)));   // (the struct only grows at its end)
     } catch (const std::bad_alloc&) {
         return BSMR_ERR_OOM;
@@ -156,8 +190,14 @@ int bsmr_blocked_check(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* row
     return BSMR_OK;
 }
 
-int bsmr_backward_attach_blocks(bsmr_backward* bw, const bsmr_rphm_desc* desc) {
+int bsmr_blocked_check(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* row_offsets, const uint32_t* col_indices,
+                       const bsmr_rphm_desc* desc, bsmr_blocked_stats* out, size_t out_size) {
+    return bsmr_blocked_check_split(M, N, nnz, row_offsets, col_indices, desc, 0, out, out_size);
+}
+
+int bsmr_backward_attach_blocks_split(bsmr_backward* bw, const bsmr_rphm_desc* desc, uint32_t segment_blocks) {
     if (!bw || !desc || bw->blocked) return BSMR_ERR_INVALID_ARG;
+    const uint32_t S = segment_blocks;
     const uint32_t M = bw->M, nnz = bw->nnz;
     constexpr uint32_t C = BSMR_BACKWARD_CHUNK;
     std::unique_ptr<BwBlocked> f;
@@ -168,16 +208,28 @@ int bsmr_backward_attach_blocks(bsmr_backward* bw, const bsmr_rphm_desc* desc) {
         BSMR_HIP(hipMemcpy(ro.data(), bw->rowOffsets, ro.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (nnz) BSMR_HIP(hipMemcpy(ci.data(), bw->colIndices, (size_t)nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
         BlockedHost h;
-        if (int st = blockedCheck(M, bw->N, nnz, ro.data(), ci.data(), desc, h)) return st;
+        if (int st = blockedCheck(M, bw->N, nnz, ro.data(), ci.data(), desc, S, h)) return st;
 
         const uint32_t P = desc->num_row_panels, rowsIn = desc->num_nonzero_rows;
         const uint32_t* bo = desc->block_offsets;
         std::vector<bsmr::BlkPanel> panels;
+        std::vector<bsmr::BlkSegment> segs;          // S >= 1 only
+        std::vector<bsmr::BlkSplit> splitPanels;
+        uint32_t partials = 0;                       // at most one per block
         std::vector<uint32_t> panelRows, stageRow(M, bsmr::kBlkNull);   // stageRow[r]: staging row of r, or none
         for (uint32_t p = 0; p < P; ++p) {
             if (bo[p + 1] == bo[p]) continue;
             const uint32_t q = (uint32_t)panels.size();
-            panels.push_back({bo[p], bo[p + 1] - bo[p]});
+            const uint32_t nb = bo[p + 1] - bo[p];
+            panels.push_back({bo[p], nb});
+            if (S && nb > S) {
+                const uint32_t count = (uint32_t)segmentsOf(nb, S);
+                splitPanels.push_back({q, partials, count});
+                for (uint32_t k = 0, first = bo[p]; k < count; ++k, first += S)
+                    segs.push_back({first, std::min(S, bo[p + 1] - first), q, partials++});
+            } else if (S) {
+                segs.push_back({bo[p], nb, q, bsmr::kBlkNull});
+            }
             for (uint32_t i = 0; i < 16; ++i) {
                 const uint32_t r = 16u * p + i < rowsIn ? desc->reordered_rows[16u * p + i] : bsmr::kBlkNull;
                 panelRows.push_back(r);
@@ -233,6 +285,10 @@ int bsmr_backward_attach_blocks(bsmr_backward* bw, const bsmr_rphm_desc* desc) {
         f->stats = h.stats;
         f->numPanels = (uint32_t)panels.size();
         f->numSlots = (uint32_t)slots;
+        f->segmentBlocks = S;
+        f->numSegs = (uint32_t)segs.size();
+        f->numSplitPanels = (uint32_t)splitPanels.size();
+        f->numPartials = partials;
         uint64_t& bytes = f->stats.device_index_bytes;
         if (int st = upload(f->panels, panels, bytes)) return st;
         if (int st = upload(f->panelRows, panelRows, bytes)) return st;
@@ -241,6 +297,8 @@ int bsmr_backward_attach_blocks(bsmr_backward* bw, const bsmr_rphm_desc* desc) {
         if (int st = upload(f->zeros, std::vector<float>(4, 0.f), bytes)) return st;
         if (int st = upload(f->resCols, resCols, bytes)) return st;
         if (int st = upload(f->resIdx, resIdx, bytes)) return st;
+        if (int st = upload(f->segs, segs, bytes)) return st;
+        if (int st = upload(f->splitPanels, splitPanels, bytes)) return st;
         for (int l = 0; l < 2; ++l) {
             if (int st = upload(f->items[l], items[l], bytes)) return st;
             if (int st = upload(f->splits[l], splits[l], bytes)) return st;
@@ -252,6 +310,10 @@ int bsmr_backward_attach_blocks(bsmr_backward* bw, const bsmr_rphm_desc* desc) {
     }
     bw->blocked = f.release();
     return BSMR_OK;
+}
+
+int bsmr_backward_attach_blocks(bsmr_backward* bw, const bsmr_rphm_desc* desc) {
+    return bsmr_backward_attach_blocks_split(bw, desc, 0);
 }
 
 int bsmr_backward_get_blocked_stats(const bsmr_backward* bw, bsmr_blocked_stats* out, size_t out_size) {

@@ -131,7 +131,11 @@ class BlockedStats(C.Structure):
     _fields_ = [("panels", C.c_uint32), ("panels_with_blocks", C.c_uint32), ("blocks", C.c_uint64),
                 ("block_entries", C.c_uint64), ("padding_columns", C.c_uint64), ("residue_entries", C.c_uint64),
                 ("max_residue_row", C.c_uint32), ("split_residue_rows", C.c_uint32), ("max_blocks_per_panel", C.c_uint32),
-                ("residue_items", C.c_uint32), ("device_index_bytes", C.c_uint64)]
+                ("residue_items", C.c_uint32), ("device_index_bytes", C.c_uint64),
+                # segment_blocks = S of bsmr_blocked_check_split / bsmr_backward_attach_blocks_split (S = 0: 0, 0,
+                # panels_with_blocks, max_blocks_per_panel)
+                ("segment_blocks", C.c_uint32), ("split_panels", C.c_uint32), ("segments", C.c_uint32),
+                ("max_blocks_per_segment", C.c_uint32)]
 
 
 class Timing(C.Structure):
@@ -230,7 +234,10 @@ HIP_SYMBOLS = {
                                          C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_blocked_check": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RphmDesc),
                                      C.POINTER(BlockedStats), C.c_size_t]),
+    "bsmr_blocked_check_split": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RphmDesc),
+                                           C.c_uint32, C.POINTER(BlockedStats), C.c_size_t]),
     "bsmr_backward_attach_blocks": (C.c_int, [C.c_void_p, C.POINTER(RphmDesc)]),
+    "bsmr_backward_attach_blocks_split": (C.c_int, [C.c_void_p, C.POINTER(RphmDesc), C.c_uint32]),
     "bsmr_backward_get_blocked_stats": (C.c_int, [C.c_void_p, C.POINTER(BlockedStats), C.c_size_t]),
     "bsmr_spmm_blocked": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "bsmr_spmm_blocked_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
@@ -811,25 +818,29 @@ def sddmm_backward_16(bw, K: int, dP_ptr: int, A16_ptr: int, B16_ptr: int, dA16_
 
 
 # --- blocked SpMM: Y = S_v X over the RPHM's dense blocks (fp32 MFMA) + the gather over the residue ---
-def blocked_check_status(rows, cols, row_offsets, col_indices, arrays: dict):
-    """bsmr_blocked_check (host only): (status, statistics as a dict) of RPHM-layout arrays against a CSR"""
+def blocked_check_status(rows, cols, row_offsets, col_indices, arrays: dict, segment_blocks: int = 0):
+    """bsmr_blocked_check_split (host only; segment_blocks = 0 is bsmr_blocked_check): (status, statistics as a dict) of
+    RPHM-layout arrays against a CSR"""
     ro = np.ascontiguousarray(row_offsets, dtype=np.uint32)
     ci = np.ascontiguousarray(col_indices, dtype=np.uint32)
     d, keep = rphm_desc(rows, cols, int(ci.size), arrays)
     s = BlockedStats()
-    st = hip().bsmr_blocked_check(rows, cols, ci.size, _ptr(ro), _ptr(ci) if ci.size else None, C.byref(d), C.byref(s),
-                                  C.sizeof(s))
+    st = hip().bsmr_blocked_check_split(rows, cols, ci.size, _ptr(ro), _ptr(ci) if ci.size else None, C.byref(d),
+                                        segment_blocks, C.byref(s), C.sizeof(s))
     return st, {k: getattr(s, k) for k, _ in BlockedStats._fields_}
 
 
-def backward_attach_blocks_status(bw, rows, cols, nnz, arrays: dict) -> int:
+def backward_attach_blocks_status(bw, rows, cols, nnz, arrays: dict, segment_blocks: int = 0) -> int:
     d, keep = rphm_desc(rows, cols, nnz, arrays)
-    return hip().bsmr_backward_attach_blocks(bw, C.byref(d))
+    return hip().bsmr_backward_attach_blocks_split(bw, C.byref(d), segment_blocks)
 
 
-def backward_attach_blocks(bw, rows, cols, nnz, arrays: dict):
-    """bsmr_backward_attach_blocks: the handle serves spmm_blocked afterwards (arrays: Pipeline.arrays())"""
-    _check(backward_attach_blocks_status(bw, rows, cols, nnz, arrays), "bsmr_backward_attach_blocks")
+def backward_attach_blocks(bw, rows, cols, nnz, arrays: dict, segment_blocks: int = 0):
+    """bsmr_backward_attach_blocks_split: the handle serves spmm_blocked afterwards (arrays: Pipeline.arrays()).
+    segment_blocks = S >= 1 cuts every panel's block list into segments of S blocks, each a wave's chain of its own, their
+    sums added in order (another summation order for the panels with more than S blocks); 0, the default, is
+    bsmr_backward_attach_blocks: no splitting"""
+    _check(backward_attach_blocks_status(bw, rows, cols, nnz, arrays, segment_blocks), "bsmr_backward_attach_blocks_split")
 
 
 def backward_blocked_stats(bw) -> dict:

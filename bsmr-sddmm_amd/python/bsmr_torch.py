@@ -33,6 +33,11 @@ blocks on the fp32 MFMA, one read of a row of X per block instead of one per ent
 function, another summation order (include/bsmr_hip.h "Blocked SpMM": the result depends on the reordering; an empty block
 cell meets a non-finite X as 0 * x).  The transposed spmm, dB, softmax, softmax_spmm and every SDDMM are untouched.
 blocked=True needs gather_mode=COMPUTE_F32 (ValueError otherwise).
+segment_blocks (default 0: the bits of blocked=True as without the argument) = S >= 1 attaches with
+bsmr_backward_attach_blocks_split: a panel's block list is cut into segments of S blocks, one wave each, whose fp32 sums
+are added in segment order, so a panel with many blocks is no longer one serial loop.  Panels with more than S blocks get
+another summation order (the header's "Blocked SpMM", Segment chain).  It must be an int >= 0, and a non-zero value needs
+blocked=True (ValueError otherwise).
 
 gather_mode (default COMPUTE_F32: every result bit for bit as without the argument) is the format in which the gathers
 read their operand rows: with COMPUTE_F16 / COMPUTE_BF16 spmm's X, the dY of its dX, and the B / A of sddmm's dA / dB are
@@ -70,12 +75,17 @@ _MODE16 = {torch.float16: eng.COMPUTE_F16, torch.bfloat16: eng.COMPUTE_BF16}   #
 
 class SparseOperator:
     def __init__(self, csr: "eng.CSR", alpha=0.3, delta=0.3, mode=eng.COMPUTE_F16, device=0, gather_mode=eng.COMPUTE_F32,
-                 blocked=False):
+                 blocked=False, segment_blocks=0):
         if gather_mode not in (eng.COMPUTE_F16, eng.COMPUTE_BF16, eng.COMPUTE_F32):
             raise ValueError(f"gather_mode: {gather_mode!r} is not one of COMPUTE_F16, COMPUTE_BF16, COMPUTE_F32")
         if blocked and gather_mode != eng.COMPUTE_F32:
             raise ValueError("blocked=True needs gather_mode=COMPUTE_F32: the blocked SpMM has no rounding-pass form")
+        if not isinstance(segment_blocks, int) or isinstance(segment_blocks, bool) or not 0 <= segment_blocks < 2 ** 32:
+            raise ValueError(f"segment_blocks: {segment_blocks!r} is not an int in [0, 2^32)")
+        if segment_blocks and not blocked:
+            raise ValueError("segment_blocks needs blocked=True: it splits the panels of the blocked SpMM")
         self.blocked = bool(blocked)
+        self.segment_blocks = segment_blocks
         self.csr = csr
         self.M, self.N, self.nnz = csr.rows, csr.cols, csr.nnz
         self.mode = mode
@@ -89,7 +99,7 @@ class SparseOperator:
         self._bw = eng.backward_create(self.M, self.N, csr.row_offsets, csr.col_indices,
                                        row_order=self.pipeline.array("reorderedRows"), device=device)
         if self.blocked:
-            eng.backward_attach_blocks(self._bw, self.M, self.N, self.nnz, self.pipeline.arrays())
+            eng.backward_attach_blocks(self._bw, self.M, self.N, self.nnz, self.pipeline.arrays(), segment_blocks)
 
     def __del__(self):
         if getattr(self, "_bw", None):

@@ -43,7 +43,7 @@
  *                           fp16 / bf16 tensors only - 16-bit operands in, 16-bit Y / dA / dB out, the values stay fp32
  *   bsmr_sparse_softmax / bsmr_sparse_softmax_backward
  *                        <- no reference counterpart: the row softmax over S's pattern and its gradient
- *   bsmr_blocked_check / bsmr_backward_attach_blocks / bsmr_spmm_blocked / bsmr_spmm_blocked_16
+ *   bsmr_blocked_check[_split] / bsmr_backward_attach_blocks[_split] / bsmr_spmm_blocked / bsmr_spmm_blocked_16
  *                        <- no reference counterpart: Y = S_v X over the RPHM's dense 16 x 16 blocks on the fp32 MFMA
  *   bsmr_mem_info        <- cudaMemGetInfo in calculateBlockSize (src/rowReordering.cu:1010-1013)
  *   bsmr_dev_alloc / bsmr_dev_free / bsmr_memcpy_h2d / bsmr_memcpy_d2h / bsmr_dev_memset
@@ -774,6 +774,19 @@ int bsmr_sparse_attention_backward_16(bsmr_backward *bw, uint32_t Kv, float scal
  * values; Y16 = round(Y) is applied once, after the final addition (B and R are added in fp32), with the casts of
  * bsmr_spmm_16.
  *
+ * Split panels.  bsmr_backward_attach_blocks_split takes segment_blocks = S.  S = 0 means no splitting: the contract above,
+ * word for word.  With S >= 1 the blocks b0 .. b(nb-1) of a panel are cut into ceil(nb / S) consecutive segments of S
+ * blocks, the last one shorter, in block_offsets order, and the block chain above is replaced by
+ *   Segment chain  each segment is its own fp32 fmaf chain from +0 over its blocks in order and the positions j = 0 .. 15
+ *                inside each block, exactly as the block chain runs; empty cells and padding columns behave as above.
+ *   Block part   B[r,k] = ((p0 + p1) + p2) + ..., fp32 additions of the segment sums in segment order.
+ *   Result       Y = fl(B + R), rounded once in the 16-bit form; R is unchanged.
+ * This is the chunk rule of the residue applied to the block list with a chunk of 16 S positions.  A panel with nb <= S has
+ * one segment and keeps the unsplit bits; S >= max_blocks_per_panel reproduces bsmr_backward_attach_blocks bit for bit.
+ * The result is still bitwise reproducible, with no atomics and one writer per element (a segment of a split panel writes
+ * fp32 partial rows of the workspace, one more kernel adds them in order); the empty-cell rule is unchanged.
+ * Error bound:  (max(16 min(nb, S) + ceil(nb / S) - 1, n_r) + 4) u sum|v||x|, plus the subnormal term as above.
+ *
  * bsmr_blocked_check: host only, no device, like bsmr_csr_transpose - whether `desc` is a partition of the CSR into block
  * cells and residue entries, and its statistics.  BSMR_ERR_INVALID_ARG: a NULL argument, a CSR that bsmr_backward_create
  * would refuse, desc->M / N / nnz different from M / N / nnz.  BSMR_ERR_BAD_PLAN: a CSR index missing from, or listed twice
@@ -782,24 +795,31 @@ int bsmr_sparse_attention_backward_16(bsmr_backward *bw, uint32_t Kv, float scal
  * row, column) disagrees with the CSR; a non-monotone offset array (or one that does not start at 0); a duplicate or
  * out-of-range reordered_rows; num_row_panels other than ceil(num_nonzero_rows / 16).  Otherwise the statistics are
  * written, at most out_size bytes of them (the struct only grows at its end).
+ * bsmr_blocked_check_split is the same check with the segment statistics of S = segment_blocks filled in;
+ * bsmr_blocked_check is its S = 0 call.
  *
  * bsmr_backward_attach_blocks: runs the same check against the handle's CSR before any device call, then builds and uploads
  * the device format: per block 64 bytes of column ids and 1 KiB of cells (CSR index or null) in the lane order of the
  * kernel, per panel with blocks its rows, and the residue as per-row gather lists (every row of S has one, in ascending
  * CSR index, chunked by BSMR_BACKWARD_CHUNK; rows of panels without blocks write Y, rows of panels with blocks an fp32
- * staging row).  A second attach on one handle is BSMR_ERR_INVALID_ARG.  bsmr_backward_get_blocked_stats: the statistics
- * of the attached desc with device_index_bytes filled in; BSMR_ERR_BAD_PLAN without attached blocks.
- * Workspace: chunk partials of the residue and the staging rows, 16 K floats per panel with blocks and batch.  On a handle
- * with attached blocks bsmr_backward_reserve(K, num_batches) covers them (the layout of every other call is unchanged:
- * chunk partials first); after it the blocked calls allocate nothing and can be captured in a graph.
+ * staging row).  A second attach on one handle is BSMR_ERR_INVALID_ARG.  bsmr_backward_attach_blocks_split: the same with
+ * segment_blocks = S (any value; the handle keeps it, bsmr_spmm_blocked[_16] need no argument for it), and for S >= 1 one
+ * 16-byte record per segment and 12 bytes per split panel on top; bsmr_backward_attach_blocks is its S = 0 call, same
+ * argument rules and error codes.  bsmr_backward_get_blocked_stats: the statistics of the attached desc and S with
+ * device_index_bytes filled in; BSMR_ERR_BAD_PLAN without attached blocks.
+ * Workspace, in this order: the chunk partials of the residue [b][slots][K]; the staging rows, 16 K floats per panel with
+ * blocks and batch; the segment partials, 16 K floats per segment of a split panel and batch.  On a handle with attached
+ * blocks bsmr_backward_reserve(K, num_batches) covers all three (the layout of every other call is unchanged: chunk
+ * partials first); after it the blocked calls allocate nothing and can be captured in a graph.
  *
  * bsmr_spmm_blocked / bsmr_spmm_blocked_16 follow the argument rules of bsmr_spmm / bsmr_spmm_16 (transpose 0), checked
  * before any device work: a NULL handle is BSMR_ERR_INVALID_ARG, K = 0 or not a multiple of 32 BSMR_ERR_UNSUPPORTED_K, more
  * than 65535 batches or a compute_mode other than BSMR_COMPUTE_F16 / _BF16 BSMR_ERR_INVALID_ARG, a handle without attached
  * blocks BSMR_ERR_BAD_PLAN, then the pointers (16 bytes for X and Y, 4 for v).  num_batches = 0 is a no-op; with nnz = 0 v
  * and X may be NULL and Y is all zeros.  Nothing is read outside v and X or written outside Y (M K, N K, nnz elements, times
- * num_batches); all addresses are formed in 64 bits.  A panel is one wave's serial loop over its blocks (no panel
- * splitting): max_blocks_per_panel says how long the longest is. */
+ * num_batches); all addresses are formed in 64 bits.  One wave's serial loop runs over a panel's blocks on a handle
+ * attached with S = 0 (max_blocks_per_panel says how long the longest is) and over a segment's, at most S, with S >= 1
+ * (max_blocks_per_segment; `segments` is the number of such loops per group of 64 features and batch). */
 typedef struct bsmr_blocked_stats {
     uint32_t panels;               /* row panels of the desc                                                  */
     uint32_t panels_with_blocks;
@@ -813,10 +833,18 @@ typedef struct bsmr_blocked_stats {
     uint32_t residue_items;        /* work items of the residue gather: one per row of S (a row without residue
                                       zeroes its destination), one per chunk of a split row                   */
     uint64_t device_index_bytes;   /* bsmr_backward_get_blocked_stats: the arrays attach uploaded; 0 from bsmr_blocked_check */
+    /* split panels; with S = 0: 0, 0, panels_with_blocks, max_blocks_per_panel */
+    uint32_t segment_blocks;       /* S                                                                        */
+    uint32_t split_panels;         /* panels with more than S blocks                                           */
+    uint32_t segments;             /* work units: over the panels with blocks, the sum of ceil(nb / S)         */
+    uint32_t max_blocks_per_segment;
 } bsmr_blocked_stats;
 int bsmr_blocked_check(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t *row_offsets, const uint32_t *col_indices,
                        const bsmr_rphm_desc *desc, bsmr_blocked_stats *out, size_t out_size);
+int bsmr_blocked_check_split(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t *row_offsets, const uint32_t *col_indices,
+                             const bsmr_rphm_desc *desc, uint32_t segment_blocks, bsmr_blocked_stats *out, size_t out_size);
 int bsmr_backward_attach_blocks(bsmr_backward *bw, const bsmr_rphm_desc *desc);
+int bsmr_backward_attach_blocks_split(bsmr_backward *bw, const bsmr_rphm_desc *desc, uint32_t segment_blocks);
 int bsmr_backward_get_blocked_stats(const bsmr_backward *bw, bsmr_blocked_stats *out, size_t out_size);
 int bsmr_spmm_blocked(bsmr_backward *bw, uint32_t K, const float *v_dev, const float *X_dev, float *Y_dev,
                       uint32_t num_batches, void *stream);
