@@ -16,53 +16,40 @@
 // blocks (destination = the row of Y), [1] the rows of panels with blocks (destination = their staging row); the chunk
 // slots of both are numbered through.  segs / splitPanels exist only on a handle attached with segment_blocks >= 1.
 struct BwBlocked {
-    bsmr::BlkPanel* panels = nullptr;   // [numPanels]      panels with blocks
-    uint32_t* panelRows = nullptr;      // [16 numPanels]   row of S or kBlkNull
-    bsmr::u32x4* cells = nullptr;       // [64 blocks]      cells[b][lane][s]
-    bsmr::u32x4* cols = nullptr;        // [4 blocks]       cols[b][k][s]
-    float* zeros = nullptr;             // [4]              +0: what an empty cell and a padding column load
-    uint32_t* resCols = nullptr;        // [residue]        s(t) of the residue lists: row by row, ascending CSR index
-    uint32_t* resIdx = nullptr;         // [residue]        e(t)
-    bsmr::BwItem* items[2] = {nullptr, nullptr};
-    bsmr::BwSplit* splits[2] = {nullptr, nullptr};
-    bsmr::BlkSegment* segs = nullptr;       // [numSegs]        segment_blocks >= 1: the work units, panel by panel
-    bsmr::BlkSplit* splitPanels = nullptr;  // [numSplitPanels] the panels cut into two or more segments
+    DevArray<bsmr::BlkPanel> panels;    // [numPanels]      panels with blocks
+    DevArray<uint32_t> panelRows;       // [16 numPanels]   row of S or kBlkNull
+    DevArray<bsmr::u32x4> cells;        // [64 blocks]      cells[b][lane][s]
+    DevArray<bsmr::u32x4> cols;         // [4 blocks]       cols[b][k][s]
+    DevArray<float> zeros;              // [4]              +0: what an empty cell and a padding column load
+    DevArray<uint32_t> resCols;         // [residue]        s(t) of the residue lists: row by row, ascending CSR index
+    DevArray<uint32_t> resIdx;          // [residue]        e(t)
+    DevArray<bsmr::BwItem> items[2];
+    DevArray<bsmr::BwSplit> splits[2];
+    DevArray<bsmr::BlkSegment> segs;        // [numSegs]        segment_blocks >= 1: the work units, panel by panel
+    DevArray<bsmr::BlkSplit> splitPanels;   // [numSplitPanels] the panels cut into two or more segments
     uint32_t numPanels = 0, numItems[2] = {0, 0}, numSplits[2] = {0, 0}, numSlots = 0;
     uint32_t segmentBlocks = 0, numSegs = 0, numSplitPanels = 0, numPartials = 0;   // numPartials: segments of split panels
     bsmr_blocked_stats stats{};
-
-    ~BwBlocked() {
-        for (void* p : {(void*)panels, (void*)panelRows, (void*)cells, (void*)cols, (void*)zeros, (void*)resCols, (void*)resIdx,
-                        (void*)items[0], (void*)items[1], (void*)splits[0], (void*)splits[1], (void*)segs, (void*)splitPanels})
-            if (p) (void)hipFree(p);
-    }
 };
 
 struct bsmr_backward {
     int device = 0;
     uint32_t M = 0, N = 0, nnz = 0;
-    uint32_t* rowOffsets = nullptr;   // [M+1]  S's row offsets (the softmax, csrc/softmax_capi.hpp)
-    uint32_t* colIndices = nullptr;   // [nnz]  s(t) of the row direction
-    uint32_t* cscRows = nullptr;      // [nnz]  s(t) of the column direction
-    uint32_t* cscToCsr = nullptr;     // [nnz]  e(t) of the column direction
-    bsmr::BwItem* items[2] = {nullptr, nullptr};
-    bsmr::BwSplit* splits[2] = {nullptr, nullptr};
+    DevArray<uint32_t> rowOffsets;    // [M+1]  S's row offsets (the softmax, csrc/softmax_capi.hpp)
+    DevArray<uint32_t> colIndices;    // [nnz]  s(t) of the row direction
+    DevArray<uint32_t> cscRows;       // [nnz]  s(t) of the column direction
+    DevArray<uint32_t> cscToCsr;      // [nnz]  e(t) of the column direction
+    DevArray<bsmr::BwItem> items[2];
+    DevArray<bsmr::BwSplit> splits[2];
     uint32_t numItems[2] = {0, 0}, numSplits[2] = {0, 0}, numSlots[2] = {0, 0}, maxLen[2] = {0, 0};
     bool permuteV = true;             // dB reads dP permuted into CSC order by a pass of its own (measured faster on 3 of
                                       // the 4 lab shapes); BSMR_BACKWARD_PERMUTE=0: through csc_to_csr in place
     uint64_t indexBytes = 0;
     int lanes16 = 0;                  // elements per lane of spmmGather16: 0 = the measured choice per slice width
                                       // (DESIGN 11); BSMR_GATHER16_LANES=4 / 8 at create: that layout for every width
-    float* work = nullptr;            // chunk partials (+ permuted dP) (+ 16-bit copies of the gathered operands),
+    DevArray<float> work;             // chunk partials (+ permuted dP) (+ 16-bit copies of the gathered operands),
     uint64_t workFloats = 0;          // grown on demand
-    BwBlocked* blocked = nullptr;     // bsmr_backward_attach_blocks
-
-    ~bsmr_backward() {
-        delete blocked;
-        for (void* p : {(void*)rowOffsets, (void*)colIndices, (void*)cscRows, (void*)cscToCsr, (void*)items[0], (void*)items[1],
-                        (void*)splits[0], (void*)splits[1], (void*)work})
-            if (p) (void)hipFree(p);
-    }
+    std::unique_ptr<BwBlocked> blocked;   // bsmr_backward_attach_blocks
 };
 
 namespace {
@@ -185,11 +172,9 @@ void launchGather16Out(bool map, int mode, dim3 grid, hipStream_t s, Args... arg
 
 int growWork(bsmr_backward* bw, uint64_t floats) {
     if (floats <= bw->workFloats) return BSMR_OK;
-    if (bw->work) BSMR_HIP(hipFree(bw->work));
-    bw->work = nullptr;
     bw->workFloats = 0;
-    if (!hipOk(hipMalloc(reinterpret_cast<void**>(&bw->work), floats * sizeof(float)), "hipMalloc(backward workspace)"))
-        return BSMR_ERR_OOM;
+    // (alloc frees the old workspace before it asks for the new one: the largest allocation is never held twice)
+    if (!allocOk(bw->work, floats, "hipMalloc(backward workspace)")) return BSMR_ERR_OOM;
     bw->workFloats = floats;
     return BSMR_OK;
 }

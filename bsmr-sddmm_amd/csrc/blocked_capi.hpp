@@ -308,7 +308,7 @@ int bsmr_backward_attach_blocks_split(bsmr_backward* bw, const bsmr_rphm_desc* d
     } catch (const std::bad_alloc&) {
         return BSMR_ERR_OOM;
     }
-    bw->blocked = f.release();
+    bw->blocked = std::move(f);
     return BSMR_OK;
 }
 

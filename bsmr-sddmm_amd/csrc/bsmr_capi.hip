@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_array.hpp"
 #include "cluster_kernels.hpp"
 #include "pack_device.hpp"
 #include "promote_device.hpp"
@@ -46,17 +47,17 @@ using bsmr::SparseItem;
 // Device-resident dense part for one group size H (host layout: csrc/plan_pack.hpp).
 struct DenseFormat {
     uint32_t H = 0;  // 0 = absent
-    uint32_t* groupRows = nullptr;
-    uint32_t* rowBase = nullptr;   // DIRECT: per group row; STAGED: per item row (window base)
-    uint16_t* winLen = nullptr;    // STAGED only
-    uint32_t* winMask = nullptr;   // STAGED only
-    uint32_t* blockCols = nullptr;
-    uint8_t* tiles8 = nullptr;     // STAGED destination tiles
-    bsmr::TileMask* tilesM = nullptr;   // ... in the mask form (then tiles8 is absent)
-    uint16_t* tiles16 = nullptr;   // DIRECT
-    uint32_t* tiles32 = nullptr;
-    uint8_t* blockMask = nullptr;
-    DenseItem* items = nullptr;
+    DevArray<uint32_t> groupRows;
+    DevArray<uint32_t> rowBase;   // DIRECT: per group row; STAGED: per item row (window base)
+    DevArray<uint16_t> winLen;    // STAGED only
+    DevArray<uint32_t> winMask;   // STAGED only
+    DevArray<uint32_t> blockCols;
+    DevArray<uint8_t> tiles8;     // STAGED destination tiles
+    DevArray<bsmr::TileMask> tilesM;   // ... in the mask form (then tiles8 is absent)
+    DevArray<uint16_t> tiles16;   // DIRECT
+    DevArray<uint32_t> tiles32;
+    DevArray<uint8_t> blockMask;
+    DevArray<DenseItem> items;
     uint32_t numItems = 0;
     uint32_t maxItemBlocks = 0;
     uint32_t streamWaves = 4;      // waves per workgroup of the streaming kernel (1: items of <= 8 blocks)
@@ -67,12 +68,12 @@ struct DenseFormat {
 // Device-resident dense part in the "tiles" form for one group size (host layout: csrc/tile_format.hpp).
 struct TileFormatDev {
     uint32_t H = 0;  // 0 = not built
-    uint32_t* groupRows = nullptr;
-    uint32_t* blockCols = nullptr;
-    uint32_t* blockInfo = nullptr;
-    uint32_t* entries = nullptr;
-    bsmr::TileItem* items = nullptr;
-    uint32_t* itemRowBase = nullptr;
+    DevArray<uint32_t> groupRows;
+    DevArray<uint32_t> blockCols;
+    DevArray<uint32_t> blockInfo;
+    DevArray<uint32_t> entries;
+    DevArray<bsmr::TileItem> items;
+    DevArray<uint32_t> itemRowBase;
     uint32_t numItems = 0, entryCap = 0, blocksPerItem = 0;
     uint64_t numBlocks = 0, numTiles = 0, unionColumns = 0, bytes = 0;
 };
@@ -80,11 +81,11 @@ struct TileFormatDev {
 // Device-resident dense part in the sweep form for one (panels per wave, blocks per strip) (host layout: csrc/sweep_format.hpp).
 struct SweepFormatDev {
     uint32_t W = 0, PW = 0, stripBlocks = 0;   // consumer waves, panels per wave, blocks per strip
-    uint32_t* panelRows = nullptr;
-    bsmr::SweepItem* items = nullptr;
-    uint32_t* starts = nullptr;
-    uint32_t* rowStart = nullptr;
-    uint32_t* words = nullptr;
+    DevArray<uint32_t> panelRows;
+    DevArray<bsmr::SweepItem> items;
+    DevArray<uint32_t> starts;
+    DevArray<uint32_t> rowStart;
+    DevArray<uint32_t> words;
     uint32_t numItems = 0, numGroups = 0, numStrips = 0, maxStepEntries = 0, maxItemWords = 0;
     uint64_t bytes = 0;
     bool usable = false;
@@ -93,12 +94,12 @@ struct SweepFormatDev {
 // Device-resident dense part in the GEMM form for one macro-tile shape (host layout: csrc/gemm_format.hpp).
 struct GemmFormatDev {
     uint32_t PM = 0, NB = 0;   // panels / 16-column blocks per macro-tile
-    uint32_t* panelRows = nullptr;
-    uint32_t* colOf = nullptr;
-    bsmr::GemmItem* items = nullptr;
-    uint32_t* rowStart = nullptr;
-    uint32_t* lists = nullptr;
-    uint32_t* words = nullptr;
+    DevArray<uint32_t> panelRows;
+    DevArray<uint32_t> colOf;
+    DevArray<bsmr::GemmItem> items;
+    DevArray<uint32_t> rowStart;
+    DevArray<uint32_t> lists;
+    DevArray<uint32_t> words;
     uint32_t numItems = 0, numGroups = 0, numStrips = 0;
     uint64_t numTiles = 0, bytes = 0;
     bool fullGrid = false, usable = false;
@@ -116,25 +117,25 @@ struct bsmr_plan {
     uint64_t numDenseEntries = 0;
 
     // sparse residue
-    uint32_t* panelRows = nullptr;
-    uint32_t* entryCol = nullptr;
-    uint32_t* entryDst = nullptr;
-    uint8_t* entryRow = nullptr;
-    SparseItem* sparseItems = nullptr;
+    DevArray<uint32_t> panelRows;
+    DevArray<uint32_t> entryCol;
+    DevArray<uint32_t> entryDst;
+    DevArray<uint8_t> entryRow;
+    DevArray<SparseItem> sparseItems;
     uint64_t numSparseEntries = 0;
     uint32_t numSparseItems = 0;
 
     uint64_t indexBytes = 0;
 
     // operand workspace (16-bit copies of A and B), grown on demand
-    uint16_t* A16 = nullptr;
-    uint16_t* B16 = nullptr;
+    DevArray<uint16_t> A16;
+    DevArray<uint16_t> B16;
     uint32_t reservedK = 0;
 
     int sparseLpe = 0;             // 0 = per-K tuned shape (sparseShape); BSMR_SPARSE_LPE = 4 / 8 / 16 forces the run-time loop
     bool sparseLowp = true;        // residue from the fp16/bf16 copies whenever the conversion pass runs (BSMR_SPARSE_LOWP=0: always fp32)
     bool convertInKernel = false;  // dense part so small that the full operand conversion pass does not pay
-    uint32_t* entryRowId = nullptr;  // free-form residue: row id per entry (panelRows / entryRow unused)
+    DevArray<uint32_t> entryRowId;   // free-form residue: row id per entry (panelRows / entryRow unused)
     bool sparseFree = false;
     uint64_t foldedEntries = 0;    // entries of a small dense part that were moved to the residue
     uint64_t promotedEntries = 0;  // residue entries of the RPHM that the plan computes as extra dense blocks
@@ -201,6 +202,13 @@ struct bsmr_plan {
     uint64_t delegateKey = 0;      // ... the (K << 8 | mode) it was measured for: calls with another K or mode (exact fp32
                                    // included, whose summation order follows the dense / residue split) stay with this plan
     int variantChosen = 0;         // BSMR_VARIANT_* of the plan that serves the calls
+
+    // (the device arrays free themselves - csrc/dev_array.hpp; on the plan's device, which bsmr_plan_destroy makes current)
+    ~bsmr_plan() {
+        if (sideStream) (void)hipStreamDestroy(sideStream);
+        if (forkEvent) (void)hipEventDestroy(forkEvent);
+        if (joinEvent) (void)hipEventDestroy(joinEvent);
+    }
 };
 
 namespace {
@@ -250,15 +258,20 @@ int useDevice(int device) {
     return BSMR_OK;
 }
 
+// `count` elements for `a` (what it held is freed first; 0: none); a failure is recorded under `what`
 template <typename T>
-int upload(T*& dst, const std::vector<T>& src, uint64_t& bytes) {
-    dst = nullptr;
-    if (src.empty()) return BSMR_OK;
-    const size_t n = src.size() * sizeof(T);
-    if (!hipOk(hipMalloc(reinterpret_cast<void**>(&dst), n), "hipMalloc(plan)")) return BSMR_ERR_OOM;
-    BSMR_HIP(hipMemcpy(dst, src.data(), n, hipMemcpyHostToDevice));
-    bytes += n;
-    return BSMR_OK;
+bool allocOk(DevArray<T>& a, size_t count, const char* what) {
+    hipError_t e = hipSuccess;
+    return a.alloc(count, &e) || hipOk(e, what);
+}
+
+template <typename T>
+int upload(DevArray<T>& dst, const std::vector<T>& src, uint64_t& bytes) {
+    const hipError_t e = devUpload(dst, src, bytes);
+    if (e == hipSuccess) return BSMR_OK;
+    const bool copied = dst.get() != nullptr;   // (the allocation succeeded, the copy failed)
+    hipOk(e, copied ? "hipMemcpy(plan)" : "hipMalloc(plan)");
+    return copied ? BSMR_ERR_HIP : BSMR_ERR_OOM;
 }
 
 // BSMR_PLAN_TIMING=1: the stages of a plan's construction on stderr, milliseconds each (the device is synchronised at every
@@ -317,44 +330,6 @@ int envInt(const char* name, int fallback) {
     return std::atoi(v);
 }
 
-void freePlanDevice(bsmr_plan* p) {
-    for (DenseFormat& f : p->fmt) {
-        void* ptrs[] = {f.groupRows, f.rowBase, f.winLen, f.winMask, f.blockCols, f.tiles8, f.tilesM,
-                        f.tiles16,   f.tiles32, f.blockMask, f.items};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-        f = DenseFormat{};
-    }
-    void* ptrs[] = {p->panelRows, p->entryCol, p->entryDst, p->entryRow, p->entryRowId, p->sparseItems, p->A16, p->B16};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    if (p->sideStream) (void)hipStreamDestroy(p->sideStream);
-    if (p->forkEvent) (void)hipEventDestroy(p->forkEvent);
-    if (p->joinEvent) (void)hipEventDestroy(p->joinEvent);
-    p->sideStream = nullptr;
-    p->forkEvent = p->joinEvent = nullptr;
-    for (TileFormatDev& t : p->tiles) {
-        void* tp[] = {t.groupRows, t.blockCols, t.blockInfo, t.entries, t.items, t.itemRowBase};
-        for (void* q : tp)
-            if (q) (void)hipFree(q);
-        t = TileFormatDev{};
-    }
-    for (SweepFormatDev& w : p->sweeps) {
-        void* wp[] = {w.panelRows, w.items, w.starts, w.rowStart, w.words};
-        for (void* q : wp)
-            if (q) (void)hipFree(q);
-    }
-    p->sweeps.clear();
-    p->sweepNow = -1;
-    for (GemmFormatDev& w : p->gemms) {
-        void* wp[] = {w.panelRows, w.colOf, w.items, w.rowStart, w.lists, w.words};
-        for (void* q : wp)
-            if (q) (void)hipFree(q);
-    }
-    p->gemms.clear();
-    p->gemmNow = -1;
-}
-
 int currentDevice() {
     int d = 0;
     if (hipGetDevice(&d) != hipSuccess) (void)hipGetLastError();
@@ -373,7 +348,16 @@ int raiseDynamicLds(const void* kernel, size_t bytes, int device) {
     return BSMR_OK;
 }
 
-int uploadDense(DenseFormat& f, const bsmr::PackedPlan& pk, uint64_t& bytes) {
+// The mask form of the tiles is built as 32-bit words and read as bsmr::TileMask records: the one place that says so.
+void adoptMaskWords(DevArray<bsmr::TileMask>& tiles, DevArray<uint32_t>& words) {
+    const size_t n = words.bytes() / sizeof(bsmr::TileMask);
+    tiles.adopt(reinterpret_cast<bsmr::TileMask*>(words.release()), n);
+}
+
+// `dst` and `indexBytes` change only when every array is on the device: a failed upload leaves both as they were
+int uploadDense(DenseFormat& dst, const bsmr::PackedPlan& pk, uint64_t& indexBytes) {
+    DenseFormat f;
+    uint64_t bytes = 0;
     f.H = pk.H;
     f.numItems = (uint32_t)pk.denseItems.size();
     f.maxItemBlocks = 0;
@@ -388,15 +372,18 @@ int uploadDense(DenseFormat& f, const bsmr::PackedPlan& pk, uint64_t& bytes) {
     if (st == BSMR_OK) st = upload(f.blockCols, pk.blockCols, bytes);
     if (st == BSMR_OK) st = upload(f.tiles8, pk.tiles8, bytes);
     if (st == BSMR_OK) {
-        uint32_t* words = nullptr;
+        DevArray<uint32_t> words;
         st = upload(words, pk.tilesMask, bytes);
-        f.tilesM = reinterpret_cast<bsmr::TileMask*>(words);
+        adoptMaskWords(f.tilesM, words);
     }
     if (st == BSMR_OK) st = upload(f.tiles16, pk.tiles16, bytes);
     if (st == BSMR_OK) st = upload(f.tiles32, pk.tiles32, bytes);
     if (st == BSMR_OK) st = upload(f.blockMask, pk.blockMask, bytes);
     if (st == BSMR_OK) st = upload(f.items, pk.denseItems, bytes);
-    return st;
+    if (st != BSMR_OK) return st;
+    dst = std::move(f);
+    indexBytes += bytes;
+    return BSMR_OK;
 }
 
 
@@ -407,19 +394,10 @@ struct DevicePackResult {
 constexpr int kPackOnHost = 1000;   // not a status: this input / layout is the host packer's
 
 template <typename T>
-bool keep(T*& dst, size_t count, uint64_t& bytes) {   // an array the plan keeps (counted like upload())
-    dst = nullptr;
-    if (count == 0) return true;
-    if (!hipOk(hipMalloc(reinterpret_cast<void**>(&dst), count * sizeof(T)), "hipMalloc(plan)")) return false;
-    bytes += count * sizeof(T);
+bool keep(DevArray<T>& dst, size_t count, uint64_t& bytes) {   // an array the plan keeps (counted like upload())
+    if (!allocOk(dst, count, "hipMalloc(plan)")) return false;
+    bytes += dst.bytes();
     return true;
-}
-
-void dropDense(DenseFormat& f) {
-    void* ptrs[] = {f.groupRows, f.rowBase, f.winLen, f.winMask, f.blockCols, f.tiles8, f.tilesM, f.tiles16, f.tiles32, f.blockMask, f.items};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    f = DenseFormat{};
 }
 
 // csrc/plan_promote.hpp's rule on the device (csrc/promote_device.hpp).  BSMR_OK: `applied` says whether blocks were promoted
@@ -654,23 +632,13 @@ int packDenseOnDevice(const bsmr_rphm_desc* d, const bsmr::PackOptions& opt, con
         !dev.alloc(&dLoAtFirst, (size_t)numBlocks * 16, "hipMalloc") || !dev.alloc(&dHiAtFirst, (size_t)numBlocks * 16, "hipMalloc") ||
         !dev.alloc(&dItemBefore, numBlocks, "hipMalloc"))
         return BSMR_ERR_OOM;
-    DenseFormat out;
+    DenseFormat out;   // (on any early return nothing of the half-built format survives)
     uint64_t bytes = 0;
-    uint32_t* dMaskWords = nullptr;
-    struct Undo {   // on any early return nothing of the half-built format survives
-        DenseFormat& f;
-        uint32_t*& words;
-        bool armed = true;
-        ~Undo() {
-            if (!armed) return;
-            dropDense(f);
-            if (words) (void)hipFree(words);
-        }
-    } undo{out, dMaskWords};
+    DevArray<uint32_t> dMaskWords;
     if (!keep(out.groupRows, panelRows.size(), bytes) || !keep(out.blockCols, (size_t)numBlocks * 16, bytes) ||
         !keep(out.blockMask, numBlocks, bytes) || !keep(out.tiles8, (size_t)numBlocks * 256, bytes))
         return BSMR_ERR_OOM;
-    if (!hipOk(hipMalloc(reinterpret_cast<void**>(&dMaskWords), (size_t)numBlocks * 48), "hipMalloc(plan)")) return BSMR_ERR_OOM;
+    if (!allocOk(dMaskWords, (size_t)numBlocks * 12, "hipMalloc(plan)")) return BSMR_ERR_OOM;
     BSMR_HIP(hipMemcpyAsync(out.groupRows, panelRows.data(), panelRows.size() * 4, hipMemcpyHostToDevice, s));
     BSMR_HIP(hipMemsetAsync(dIsFirst, 0, (size_t)numBlocks * 4, s));
     hipLaunchKernelGGL(bsmr::packPanelOfBlock, dim3(P), dim3(256), 0, s, dFirstBlock, P, dPanelOfBlock);
@@ -790,23 +758,19 @@ int packDenseOnDevice(const bsmr_rphm_desc* d, const bsmr::PackOptions& opt, con
         }
     }
     if (opt.maskTiles && !(flags & 4u)) {   // every tile row's offsets are consecutive: the 48-byte form
-        (void)hipFree(out.tiles8);
-        out.tiles8 = nullptr;
+        out.tiles8.reset();
         bytes -= (uint64_t)numBlocks * 256;
-        out.tilesM = reinterpret_cast<bsmr::TileMask*>(dMaskWords);
-        dMaskWords = nullptr;
+        adoptMaskWords(out.tilesM, dMaskWords);
         bytes += (uint64_t)numBlocks * 48;
     } else {
-        (void)hipFree(dMaskWords);
-        dMaskWords = nullptr;
+        dMaskWords.reset();
     }
     out.H = 1;
     out.numItems = numItems;
     out.numBlocks = numBlocks;
     out.numTiles = r.numTiles;
     out.unionColumns = r.unionColumns;
-    undo.armed = false;
-    f = out;
+    f = std::move(out);
     indexBytes += bytes;
     return BSMR_OK;
 }
@@ -1012,38 +976,31 @@ int ensureTiles(bsmr_plan* p, uint32_t H) {
         const int forcedBlocks = p->tileBlocksNow > 0 ? p->tileBlocksNow : p->opt.tile_blocks_per_item;
         if (forcedBlocks > 0) perItem = (uint32_t)std::min<int>(forcedBlocks, bsmr::kTileMaxItemBlocks);
         if (t.H && t.blocksPerItem == perItem) return BSMR_OK;
-        if (t.H) {
-            void* tp[] = {t.groupRows, t.blockCols, t.blockInfo, t.entries, t.items, t.itemRowBase};
-            for (void* q : tp)
-                if (q) (void)hipFree(q);
+        if (t.H) {   // another item length: the old format goes first, so that the two are never held together
             p->indexBytes -= t.bytes;
             t = TileFormatDev{};
         }
         bsmr::TileFormatHost host;
         int st = bsmr::packTiles(p->hostDense, H, perItem, host);
         if (st != BSMR_OK) return st;
+        TileFormatDev built;   // moved into the plan once every array is on the device
         uint64_t bytes = 0;
-        t.numItems = (uint32_t)host.items.size();
-        t.entryCap = host.entryCap;
-        t.blocksPerItem = perItem;
-        t.numBlocks = host.numBlocks;
-        t.numTiles = host.numTiles;
-        t.unionColumns = host.unionColumns;
-        st = upload(t.groupRows, host.groupRows, bytes);
-        if (st == BSMR_OK) st = upload(t.blockCols, host.blockCols, bytes);
-        if (st == BSMR_OK) st = upload(t.blockInfo, host.blockInfo, bytes);
-        if (st == BSMR_OK) st = upload(t.entries, host.entries, bytes);
-        if (st == BSMR_OK) st = upload(t.items, host.items, bytes);
-        if (st == BSMR_OK) st = upload(t.itemRowBase, host.itemRowBase, bytes);
-        if (st != BSMR_OK) {
-            void* tp[] = {t.groupRows, t.blockCols, t.blockInfo, t.entries, t.items, t.itemRowBase};
-            for (void* q : tp)
-                if (q) (void)hipFree(q);
-            t = TileFormatDev{};
-            return st;
-        }
-        t.bytes = bytes;
-        t.H = H;
+        built.numItems = (uint32_t)host.items.size();
+        built.entryCap = host.entryCap;
+        built.blocksPerItem = perItem;
+        built.numBlocks = host.numBlocks;
+        built.numTiles = host.numTiles;
+        built.unionColumns = host.unionColumns;
+        st = upload(built.groupRows, host.groupRows, bytes);
+        if (st == BSMR_OK) st = upload(built.blockCols, host.blockCols, bytes);
+        if (st == BSMR_OK) st = upload(built.blockInfo, host.blockInfo, bytes);
+        if (st == BSMR_OK) st = upload(built.entries, host.entries, bytes);
+        if (st == BSMR_OK) st = upload(built.items, host.items, bytes);
+        if (st == BSMR_OK) st = upload(built.itemRowBase, host.itemRowBase, bytes);
+        if (st != BSMR_OK) return st;
+        built.bytes = bytes;
+        built.H = H;
+        t = std::move(built);
         p->indexBytes += bytes;
         return BSMR_OK;
     } catch (const std::bad_alloc&) {
@@ -1058,17 +1015,16 @@ int launchTilesD(const TileFormatDev& t, int device, const uint16_t* A16, const 
     if (int st = raiseDynamicLds(reinterpret_cast<const void*>(kernel), lds, device)) return st;
 #ifdef BSMR_LAB_STAMPS
     if (envInt("BSMR_TILE_STAMPS", 0)) {   // lab: one stamped launch, phase statistics on stderr
-        uint64_t* dev = nullptr;
+        DevArray<uint64_t> dev;
         const size_t n = (size_t)t.numItems * 8;
-        BSMR_HIP(hipMalloc(reinterpret_cast<void**>(&dev), n * 8));
+        if (!allocOk(dev, n, "hipMalloc(stamps)")) return BSMR_ERR_HIP;
         BSMR_HIP(hipMemset(dev, 0, n * 8));
         hipLaunchKernelGGL(kernel, dim3(t.numItems, 1), dim3(bsmr::kWave), lds, s, A16, B16, t.groupRows, t.blockCols,
-                           reinterpret_cast<const uint4*>(t.blockInfo), t.entries, t.items, t.itemRowBase, P, t.entryCap,
+                           reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P, t.entryCap,
                            s.batch, dev);
         BSMR_HIP(hipStreamSynchronize(s));
         std::vector<uint64_t> h(n);
         BSMR_HIP(hipMemcpy(h.data(), dev, n * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(dev);
         uint64_t first = ~0ull, last = 0;
         for (uint32_t i = 0; i < t.numItems; ++i) {
             first = std::min(first, h[(size_t)i * 8]);
@@ -1095,11 +1051,11 @@ int launchTilesD(const TileFormatDev& t, int device, const uint16_t* A16, const 
         return BSMR_OK;
     }
     hipLaunchKernelGGL(kernel, dim3(t.numItems, s.batch.count), dim3(bsmr::kWave), lds, s, A16, B16, t.groupRows,
-                       t.blockCols, reinterpret_cast<const uint4*>(t.blockInfo), t.entries, t.items, t.itemRowBase, P,
+                       t.blockCols, reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P,
                        t.entryCap, s.batch, (uint64_t*)nullptr);
 #else
     hipLaunchKernelGGL(kernel, dim3(t.numItems, s.batch.count), dim3(bsmr::kWave), lds, s, A16, B16, t.groupRows,
-                       t.blockCols, reinterpret_cast<const uint4*>(t.blockInfo), t.entries, t.items, t.itemRowBase, P,
+                       t.blockCols, reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P,
                        t.entryCap, s.batch);
 #endif
     BSMR_HIP(hipGetLastError());
@@ -1137,16 +1093,15 @@ int launchSharedT(const TileFormatDev& t, int device, uint32_t numCols, const ui
         if (int st = raiseDynamicLds(reinterpret_cast<const void*>(kernel), lds, device)) return st;
 #ifdef BSMR_LAB_STAMPS
         if (envInt("BSMR_TILE_STAMPS", 0)) {   // lab: one stamped launch, phase statistics on stderr (one record per wave)
-            uint64_t* dev = nullptr;
+            DevArray<uint64_t> dev;
             const size_t nrec = (size_t)t.numItems * 4, n = nrec * 8;
-            BSMR_HIP(hipMalloc(reinterpret_cast<void**>(&dev), n * 8));
+            if (!allocOk(dev, n, "hipMalloc(stamps)")) return BSMR_ERR_HIP;
             BSMR_HIP(hipMemset(dev, 0, n * 8));
             hipLaunchKernelGGL(kernel, dim3(t.numItems, 1), dim3(bsmr::kThreads), lds, s, A16, B16, t.groupRows, t.blockCols,
-                               reinterpret_cast<const uint4*>(t.blockInfo), t.entries, t.items, t.itemRowBase, P, numCols, s.batch, dev);
+                               reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P, numCols, s.batch, dev);
             BSMR_HIP(hipStreamSynchronize(s));
             std::vector<uint64_t> h(n);
             BSMR_HIP(hipMemcpy(h.data(), dev, n * 8, hipMemcpyDeviceToHost));
-            (void)hipFree(dev);
             uint64_t first = ~0ull;
             for (size_t i = 0; i < nrec; ++i) first = std::min(first, h[i * 8]);
             auto med = [&](auto f) {
@@ -1170,11 +1125,11 @@ int launchSharedT(const TileFormatDev& t, int device, uint32_t numCols, const ui
             return BSMR_OK;
         }
         hipLaunchKernelGGL(kernel, dim3(t.numItems, s.batch.count), dim3(bsmr::kThreads), lds, s, A16, B16, t.groupRows,
-                           t.blockCols, reinterpret_cast<const uint4*>(t.blockInfo), t.entries, t.items, t.itemRowBase, P, numCols, s.batch,
+                           t.blockCols, reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P, numCols, s.batch,
                            (uint64_t*)nullptr);
 #else
         hipLaunchKernelGGL(kernel, dim3(t.numItems, s.batch.count), dim3(bsmr::kThreads), lds, s, A16, B16, t.groupRows,
-                           t.blockCols, reinterpret_cast<const uint4*>(t.blockInfo), t.entries, t.items, t.itemRowBase, P, numCols, s.batch);
+                           t.blockCols, reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P, numCols, s.batch);
 #endif
         BSMR_HIP(hipGetLastError());
         return BSMR_OK;
@@ -1276,11 +1231,11 @@ int ensureSweep(bsmr_plan* p, uint32_t K) {
         bsmr::SweepFormatHost host;
         int st = bsmr::packSweep(p->hostDense, W, PW, SB, host);
         if (st == BSMR_ERR_BAD_PLAN || st == BSMR_ERR_INVALID_ARG) {   // a shape this plan cannot take: remembered, the call streams
-            p->sweeps.push_back(w);
+            p->sweeps.push_back(std::move(w));
             return BSMR_OK;
         }
         if (st != BSMR_OK) return st;
-        uint64_t bytes = 0;
+        uint64_t bytes = 0;   // (w joins the plan once every array is on the device)
         w.numItems = (uint32_t)host.items.size();
         w.numGroups = host.numGroups;
         w.numStrips = host.numStrips;
@@ -1291,18 +1246,13 @@ int ensureSweep(bsmr_plan* p, uint32_t K) {
         if (st == BSMR_OK) st = upload(w.starts, host.starts, bytes);
         if (st == BSMR_OK) st = upload(w.rowStart, host.rowStart, bytes);
         if (st == BSMR_OK) st = upload(w.words, host.words, bytes);
-        if (st != BSMR_OK) {
-            void* wp[] = {w.panelRows, w.items, w.starts, w.rowStart, w.words};
-            for (void* q : wp)
-                if (q) (void)hipFree(q);
-            return st;
-        }
+        if (st != BSMR_OK) return st;
         w.bytes = bytes;
         // (the kernel keeps an item's entry words in a 32 KiB region of LDS: shorter strips, or another engine, otherwise)
         w.usable = w.numItems != 0 && host.maxItemWords + 64u <= bsmr::kSweepItemWords;
+        p->sweeps.push_back(std::move(w));
         p->indexBytes += bytes;
-        p->sweeps.push_back(w);
-        if (w.usable) p->sweepNow = (int)p->sweeps.size() - 1;
+        if (p->sweeps.back().usable) p->sweepNow = (int)p->sweeps.size() - 1;
         return BSMR_OK;
     } catch (const std::bad_alloc&) {
         return BSMR_ERR_OOM;
@@ -1443,11 +1393,11 @@ int ensureGemm(bsmr_plan* p, uint32_t K) {
         bsmr::GemmFormatHost host;
         int st = bsmr::packGemm(p->hostDense, PM, NB, host, p->opt.gemm_balance_columns != 0);
         if (st == BSMR_ERR_BAD_PLAN || st == BSMR_ERR_INVALID_ARG) {   // a shape this plan cannot take: remembered, the call uses another engine
-            p->gemms.push_back(w);
+            p->gemms.push_back(std::move(w));
             return BSMR_OK;
         }
         if (st != BSMR_OK) return st;
-        uint64_t bytes = 0;
+        uint64_t bytes = 0;   // (w joins the plan once every array is on the device)
         w.numItems = (uint32_t)host.items.size();
         w.numGroups = host.numGroups;
         w.numStrips = host.numStrips;
@@ -1459,17 +1409,12 @@ int ensureGemm(bsmr_plan* p, uint32_t K) {
         if (st == BSMR_OK) st = upload(w.rowStart, host.rowStart, bytes);
         if (st == BSMR_OK) st = upload(w.lists, host.lists, bytes);
         if (st == BSMR_OK) st = upload(w.words, host.words, bytes);
-        if (st != BSMR_OK) {
-            void* wp[] = {w.panelRows, w.colOf, w.items, w.rowStart, w.lists, w.words};
-            for (void* q : wp)
-                if (q) (void)hipFree(q);
-            return st;
-        }
+        if (st != BSMR_OK) return st;
         w.bytes = bytes;
         w.usable = w.numItems != 0;
+        p->gemms.push_back(std::move(w));
         p->indexBytes += bytes;
-        p->gemms.push_back(w);
-        if (w.usable) p->gemmNow = (int)p->gemms.size() - 1;
+        if (p->gemms.back().usable) p->gemmNow = (int)p->gemms.size() - 1;
         return BSMR_OK;
     } catch (const std::bad_alloc&) {
         return BSMR_ERR_OOM;
@@ -1841,13 +1786,14 @@ int prepareDense(bsmr_plan* p, uint32_t K, int mode) {
 
 int reserve(bsmr_plan* p, uint32_t K) {
     if (p->reservedK >= K && p->A16 && p->B16) return BSMR_OK;
-    if (p->A16) (void)hipFree(p->A16);
-    if (p->B16) (void)hipFree(p->B16);
-    p->A16 = p->B16 = nullptr;
+    p->A16.reset();   // (freed first: the two are never held in both sizes)
+    p->B16.reset();
     p->reservedK = 0;
-    const size_t a = std::max<size_t>((size_t)p->M * K * 2, 16), b = std::max<size_t>((size_t)p->N * K * 2, 16);
-    if (!hipOk(hipMalloc(reinterpret_cast<void**>(&p->A16), a), "hipMalloc(A16)")) return BSMR_ERR_OOM;
-    if (!hipOk(hipMalloc(reinterpret_cast<void**>(&p->B16), b), "hipMalloc(B16)")) return BSMR_ERR_OOM;
+    DevArray<uint16_t> a, b;   // both or neither
+    if (!allocOk(a, std::max<size_t>((size_t)p->M * K, 8), "hipMalloc(A16)")) return BSMR_ERR_OOM;
+    if (!allocOk(b, std::max<size_t>((size_t)p->N * K, 8), "hipMalloc(B16)")) return BSMR_ERR_OOM;
+    p->A16 = std::move(a);
+    p->B16 = std::move(b);
     p->reservedK = K;
     return BSMR_OK;
 }
@@ -2339,10 +2285,7 @@ int createPlan(bsmr_plan** out, int device, const bsmr_rphm_desc* d, const bsmr_
                 pk.numTiles = r.numTiles;
                 pk.unionColumns = r.unionColumns;
                 trace.mark("device packer");
-                if ((st = bsmr::packResidue(d, opt, pk)) != BSMR_OK) {
-                    dropDense(deviceFormat);
-                    return st;
-                }
+                if ((st = bsmr::packResidue(d, opt, pk)) != BSMR_OK) return st;
                 trace.mark("residue packer (host)");
                 packedOnDevice = true;
             } else if (st != kPackOnHost && st != BSMR_ERR_OOM) {   // (no room for the scratch arrays: the host packer needs none)
@@ -2386,11 +2329,7 @@ int createPlan(bsmr_plan** out, int device, const bsmr_rphm_desc* d, const bsmr_
         const float packMs = msSince(tPack);
         trace.mark("packing (all of it)");
 
-        bsmr_plan* p = new (std::nothrow) bsmr_plan;
-        if (!p) {
-            dropDense(deviceFormat);
-            return BSMR_ERR_OOM;
-        }
+        std::unique_ptr<bsmr_plan> p(new bsmr_plan);   // (every early return and exception from here on drops it, device arrays and all)
         p->device = device;
         p->packedOnDevice = packedOnDevice;
         p->promotedOnDevice = promotedOnDevice;
@@ -2417,11 +2356,7 @@ int createPlan(bsmr_plan** out, int device, const bsmr_rphm_desc* d, const bsmr_
             if ((p->useTiles || p->tunable || p->useSweep || p->useGemm) && pk.numBlocks && packedOnDevice) {
                 p->hostDense = std::move(collected);
             } else if ((p->useTiles || p->tunable || p->useSweep || p->useGemm) && pk.numBlocks) {
-                st = bsmr::collectDense(d, p->hostDense);
-                if (st != BSMR_OK) {
-                    delete p;
-                    return st;
-                }
+                if ((st = bsmr::collectDense(d, p->hostDense)) != BSMR_OK) return st;
             }
         }
         // full conversion moves 6 bytes per operand element; the in-kernel path reads each
@@ -2444,7 +2379,7 @@ int createPlan(bsmr_plan** out, int device, const bsmr_rphm_desc* d, const bsmr_
         trace.mark("dense entry lists");
         const Clock::time_point tUpload = Clock::now();
         if (packedOnDevice) {
-            p->fmt[0] = deviceFormat;
+            p->fmt[0] = std::move(deviceFormat);
             p->indexBytes += deviceFormatBytes;
             st = BSMR_OK;
         } else {
@@ -2488,8 +2423,7 @@ int createPlan(bsmr_plan** out, int device, const bsmr_rphm_desc* d, const bsmr_
         // (a plan that defers the format also defers the count of the grouped columns: ensureGrouped takes it from the lists)
         const uint64_t grouped4 = groupedPossible && !deferGrouped ? bsmr::countUnionColumns(d, 4) : 0;
         if (grouped4 && pk.unionColumns * 2 >= 5 * grouped4 && (promotedOnDevice || denseResident) && !deferGrouped) {   // (the host packer builds that one: it needs the values)
-            freePlanDevice(p);
-            delete p;
+            p.reset();   // (before the other plan is built)
             if (res) return kPackOnHost;
             bsmr_plan_options again = o;
             again.promote_on_device = 0;
@@ -2510,11 +2444,7 @@ int createPlan(bsmr_plan** out, int device, const bsmr_rphm_desc* d, const bsmr_
                 st = uploadDense(p->fmt[1], pk4, p->indexBytes);
             p->fmt[1].stageInLds = outputMode == 2;
         }
-        if (st != BSMR_OK) {
-            freePlanDevice(p);
-            delete p;
-            return st;
-        }
+        if (st != BSMR_OK) return st;
         p->buildMs[3] = msSince(tSecond);
         p->buildMs[4] = msSince(tStart);
         trace.mark("uploads + second format");
@@ -2544,7 +2474,7 @@ int createPlan(bsmr_plan** out, int device, const bsmr_rphm_desc* d, const bsmr_
             keep->desc.sparse_col_indices = keep->sparseCols.data();
             p->retained = std::move(keep);
         }
-        *out = p;
+        *out = p.release();
         return BSMR_OK;
     } catch (const std::bad_alloc&) {
         return BSMR_ERR_OOM;
@@ -2565,7 +2495,6 @@ int bsmr_plan_destroy(bsmr_plan* plan) {
         plan->delegate = nullptr;
     }
     if (hipSetDevice(plan->device) != hipSuccess) (void)hipGetLastError();
-    freePlanDevice(plan);
     delete plan;
     return BSMR_OK;
 }
@@ -3371,30 +3300,19 @@ int bsmr_sddmm_host(bsmr_plan* plan, uint32_t K, const float* A_host, const floa
     if (iters <= 0) iters = 1;
     BSMR_HIP(hipSetDevice(plan->device));
     const size_t aBytes = (size_t)plan->M * K * 4, bBytes = (size_t)plan->N * K * 4, pBytes = (size_t)plan->nnz * 4;
-    float *A = nullptr, *B = nullptr, *P = nullptr;
-    auto cleanup = [&]() {
-        if (A) (void)hipFree(A);
-        if (B) (void)hipFree(B);
-        if (P) (void)hipFree(P);
-    };
-    if (!hipOk(hipMalloc(reinterpret_cast<void**>(&A), std::max<size_t>(aBytes, 16)), "hipMalloc(A)") ||
-        !hipOk(hipMalloc(reinterpret_cast<void**>(&B), std::max<size_t>(bBytes, 16)), "hipMalloc(B)") ||
-        !hipOk(hipMalloc(reinterpret_cast<void**>(&P), std::max<size_t>(pBytes, 16)), "hipMalloc(P)")) {
-        cleanup();
+    DevArray<float> A, B, P;   // (at least 16 bytes each)
+    if (!allocOk(A, std::max<size_t>(aBytes, 16) / 4, "hipMalloc(A)") || !allocOk(B, std::max<size_t>(bBytes, 16) / 4, "hipMalloc(B)") ||
+        !allocOk(P, std::max<size_t>(pBytes, 16) / 4, "hipMalloc(P)"))
         return BSMR_ERR_OOM;
-    }
     if (!hipOk(hipMemcpy(A, A_host, aBytes, hipMemcpyHostToDevice), "h2d A") ||
         !hipOk(hipMemcpy(B, B_host, bBytes, hipMemcpyHostToDevice), "h2d B") ||
-        !hipOk(hipMemset(P, 0, std::max<size_t>(pBytes, 16)), "memset P")) {
-        cleanup();
+        !hipOk(hipMemset(P, 0, P.bytes()), "memset P"))
         return BSMR_ERR_HIP;
-    }
     bsmr_timing t{};
     st = bsmr_sddmm_timed(plan, K, A, B, P, mode, nullptr, 1, iters, &t);
     if (st == BSMR_OK && pBytes && !hipOk(hipMemcpy(P_host, P, pBytes, hipMemcpyDeviceToHost), "d2h P"))
         st = BSMR_ERR_HIP;
     if (st == BSMR_OK && ms_per_iter) *ms_per_iter = t.total_ms;
-    cleanup();
     return st;
 }
 

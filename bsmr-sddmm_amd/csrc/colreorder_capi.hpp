@@ -142,15 +142,11 @@ struct bsmr_colreorder {
     uint64_t numDenseCols = 0, numSparseCols = 0, numBlocks = 0, numSparseEntries = 0;
     float elapsedMs = 0.0f;
     // device results, fetched by bsmr_col_reorder_fetch
-    uint32_t *denseCols = nullptr, *sparseCols = nullptr, *blockValues = nullptr, *sparseValues = nullptr,
-             *sparseRows = nullptr, *sparseColIdx = nullptr;
+    DevArray<uint32_t> denseCols, sparseCols, blockValues, sparseValues, sparseRows, sparseColIdx;
     std::vector<uint32_t> denseColOffsets, sparseColOffsets, sparseValueOffsets, blockOffsets;   // host (small)
     // (the result owns its device arrays: an early return of bsmr_col_reorder drops a half-built one through unique_ptr)
     ~bsmr_colreorder() {
-        if (hipSetDevice(device) != hipSuccess) (void)hipGetLastError();
-        void* ptrs[] = {denseCols, sparseCols, blockValues, sparseValues, sparseRows, sparseColIdx};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
+        if (hipSetDevice(device) != hipSuccess) (void)hipGetLastError();   // (the arrays are freed after this body)
     }
 };
 
@@ -321,14 +317,12 @@ int bsmr_col_reorder(bsmr_colreorder** out, int device, uint32_t rows, uint32_t 
         BSMR_HIP(hipMemcpyAsync(dValueOff, h->sparseValueOffsets.data(), ((size_t)P + 1) * 4, hipMemcpyHostToDevice, s));
         BSMR_HIP(hipMemcpyAsync(dBlockOff, h->blockOffsets.data(), ((size_t)P + 1) * 4, hipMemcpyHostToDevice, s));
         // 5. the arrays
-        auto allocOut = [&](uint32_t** ptr, uint64_t count) {
-            return hipOk(hipMalloc(reinterpret_cast<void**>(ptr), std::max<size_t>((size_t)count * 4, 16)), "hipMalloc(col reorder output)");
+        auto allocOut = [&](DevArray<uint32_t>& a, uint64_t count) {   // (at least 16 bytes)
+            return allocOk(a, std::max<size_t>((size_t)count, 4), "hipMalloc(col reorder output)");
         };
-        if (!allocOut(&h->denseCols, td) || !allocOut(&h->sparseCols, ts) || !allocOut(&h->blockValues, tb * 256) ||
-            !allocOut(&h->sparseValues, te) || !allocOut(&h->sparseRows, te) || !allocOut(&h->sparseColIdx, te)) {
-            bsmr_col_reorder_free(h.release());
+        if (!allocOut(h->denseCols, td) || !allocOut(h->sparseCols, ts) || !allocOut(h->blockValues, tb * 256) ||
+            !allocOut(h->sparseValues, te) || !allocOut(h->sparseRows, te) || !allocOut(h->sparseColIdx, te))
             return BSMR_ERR_OOM;
-        }
         auto fill = [&](uint32_t* ptr, uint64_t count, uint32_t v) {
             if (count) hipLaunchKernelGGL(bsmr::fillU32, dim3((unsigned)std::min<uint64_t>((count + 255) / 256, 65535)), dim3(256), 0, s, ptr, (size_t)count, v);
         };
