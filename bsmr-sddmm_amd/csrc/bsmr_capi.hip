@@ -1497,6 +1497,9 @@ inline bool cvtInKernel(const bsmr_plan* p, uint32_t K) {
 }
 inline bool convertPassOf(const bsmr_plan* p, uint32_t K) {
     if (cvtInKernel(p, K)) return false;   // (the residue of such a call runs its fp32 kernel)
+    // (a tuned b_only = 0 on a plan without a dense part is the fp32 residue kernel, also where the plan's own rule - a
+    // residue of more than 10 entries per operand row - would have converted both operands)
+    if (p->bOnlyNow == 0 && p->fmt[0].numItems == 0) return false;
     return p->fmt[0].numItems != 0 || p->convertPass;
 }
 inline bool tilesEngine(const bsmr_plan* p, uint32_t K) {
@@ -3165,6 +3168,9 @@ int bsmr_plan_set_tuned(bsmr_plan* plan, uint32_t K, int mode, const bsmr_tuned_
     if (!engineOk || t.group < 0 || t.blocksPerItem < 0 || t.format < -1 || t.format > 1 || t.bOnly < -1 || t.bOnly > 1 ||
         t.overlap < -1 || t.overlap > 1 || t.cvt < -1 || t.cvt > 1 || t.waves < 0)
         return BSMR_ERR_INVALID_ARG;
+    // (the tiles and shared-B kernels read the 16-bit copies only: with cvt_in_kernel = 1 tilesEngine would decline and the call
+    // would stream - a combination no call can honour is refused, whatever the plan)
+    if ((t.engine == BSMR_ENGINE_TILES || t.engine == BSMR_ENGINE_SHARED) && t.cvt == 1) return BSMR_ERR_INVALID_ARG;
     if (t.format == 1 && !plan->fmt[1].H && plan->groupedDeferred) {
         BSMR_HIP(hipSetDevice(plan->device));
         const int gs = ensureGrouped(plan);

@@ -330,7 +330,11 @@ int bsmr_plan_tune_sized(bsmr_plan *plan, uint32_t K, const float *A_dev, const 
  * (BSMR_ERR_INVALID_ARG when that (K, mode) was never tuned), bsmr_plan_set_tuned installs one WITHOUT timing anything -
  * a second process (a profiler pass, a later run on the same matrix) replays the measured choice of the first and launches
  * exactly its kernels.  The choice is validated (the engine must serve this K and its device format must be buildable:
- * BSMR_ERR_INVALID_ARG / BSMR_ERR_BAD_PLAN otherwise, the plan unchanged).  Plans created with k_hint keep their variant:
+ * BSMR_ERR_INVALID_ARG / BSMR_ERR_BAD_PLAN otherwise, the plan unchanged).  Refused: a field outside its range, an engine with
+ * cvt_in_kernel = 1 that has no fp32-operand kernel for this K (_TILES and _SHARED have none at any K: BSMR_ERR_INVALID_ARG;
+ * _STREAM K = 32 / 64 / 128, _SWEEP K <= 128, _GEMM K = 64 / 128 and not the 16 x 12 macro-tile), an engine other than _STREAM
+ * on a plan without a dense part or at a K it does not serve, a GEMM macro-tile no kernel is built for, format = 1 where the
+ * plan has no grouped format (BSMR_ERR_BAD_PLAN).  Plans created with k_hint keep their variant:
  * these two calls address the engines of the plan that serves the calls.  The reference has no counterpart. */
 typedef struct bsmr_tuned_choice {
     uint32_t struct_size;     /* sizeof(bsmr_tuned_choice) of the caller */
