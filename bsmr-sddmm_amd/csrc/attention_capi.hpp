@@ -43,6 +43,35 @@ int checkAttentionCall(const bsmr_backward* bw, uint32_t Kv, float scale, bool m
 
 uint32_t attnShortBlocks(const bsmr_backward* bw) { return (uint32_t)(((uint64_t)bw->M + 3u) / 4u); }
 
+// m of every row: the pass in front of the gather
+int launchAttnRowMax(const bsmr_backward* bw, float scale, const float* P, float* m, uint32_t nb, hipStream_t s) {
+    const uint32_t shortBlocks = attnShortBlocks(bw);
+    if (shortBlocks + bw->numSplits[0]) {
+        hipLaunchKernelGGL(bsmr::attnRowMax, dim3(shortBlocks + bw->numSplits[0], nb), dim3(256), 0, s, bw->rowOffsets,
+                           bw->splits[0], bw->M, shortBlocks, scale, P, m, (uint64_t)bw->nnz);
+        BSMR_HIP(hipGetLastError());
+    }
+    return BSMR_OK;
+}
+
+// The split rows: the pass behind the gather.  mode: BSMR_COMPUTE_F32 for an fp32 O, else its 16-bit format.
+int launchAttnReduce(const bsmr_backward* bw, uint32_t Kv, const float* partial, const float* sPart, const float* m, void* O,
+                     float* sOut, uint32_t nb, int mode, hipStream_t s) {
+    if (bw->numSplits[0]) {
+        const uint64_t threads = (uint64_t)bw->numSplits[0] * (Kv / 4u);
+        const dim3 rgrid((uint32_t)((threads + 255u) / 256u), nb);
+#define BSMR_ATTN_REDUCE(MODE)                                                                                            \
+    hipLaunchKernelGGL(bsmr::attnReduce<MODE>, rgrid, dim3(256), 0, s, bw->splits[0], bw->numSplits[0], partial, sPart,  \
+                       m, O, sOut, Kv, bw->M, bw->numSlots[0])
+        if (mode == BSMR_COMPUTE_F16) BSMR_ATTN_REDUCE(0);
+        else if (mode == BSMR_COMPUTE_BF16) BSMR_ATTN_REDUCE(1);
+        else BSMR_ATTN_REDUCE(-1);
+#undef BSMR_ATTN_REDUCE
+        BSMR_HIP(hipGetLastError());
+    }
+    return BSMR_OK;
+}
+
 // mode: BSMR_COMPUTE_F32 for fp32 V / O, else the 16-bit format of both
 int runAttention(bsmr_backward* bw, uint32_t Kv, float scale, const float* P, const void* V, void* O, float* m, float* sOut,
                  uint32_t nb, int mode, hipStream_t s) {
@@ -51,12 +80,7 @@ int runAttention(bsmr_backward* bw, uint32_t Kv, float scale, const float* P, co
     float* sPart = bw->work + attnSumsOffset(bw, Kv, nb);
     const uint32_t M = bw->M, slots = bw->numSlots[0];
     const uint64_t nnz = bw->nnz, xB = (uint64_t)bw->N * Kv;
-    const uint32_t shortBlocks = attnShortBlocks(bw);
-    if (shortBlocks + bw->numSplits[0]) {
-        hipLaunchKernelGGL(bsmr::attnRowMax, dim3(shortBlocks + bw->numSplits[0], nb), dim3(256), 0, s, bw->rowOffsets,
-                           bw->splits[0], M, shortBlocks, scale, P, m, nnz);
-        BSMR_HIP(hipGetLastError());
-    }
+    if (int st = launchAttnRowMax(bw, scale, P, m, nb, s)) return st;
     const uint32_t W = Kv % 256u == 0 ? 256u : Kv % 128u == 0 ? 128u : Kv % 64u == 0 ? 64u : 32u;
     const uint32_t slices = Kv / W;
     const uint64_t units = (uint64_t)bw->numItems[0] * slices;
@@ -99,19 +123,7 @@ int runAttention(bsmr_backward* bw, uint32_t Kv, float scale, const float* P, co
 #undef BSMR_ATTN_LAUNCH
         BSMR_HIP(hipGetLastError());
     }
-    if (bw->numSplits[0]) {
-        const uint64_t threads = (uint64_t)bw->numSplits[0] * (Kv / 4u);
-        const dim3 rgrid((uint32_t)((threads + 255u) / 256u), nb);
-#define BSMR_ATTN_REDUCE(MODE)                                                                                            \
-    hipLaunchKernelGGL(bsmr::attnReduce<MODE>, rgrid, dim3(256), 0, s, bw->splits[0], bw->numSplits[0], partial, sPart,  \
-                       m, O, sOut, Kv, M, slots)
-        if (mode == BSMR_COMPUTE_F16) BSMR_ATTN_REDUCE(0);
-        else if (mode == BSMR_COMPUTE_BF16) BSMR_ATTN_REDUCE(1);
-        else BSMR_ATTN_REDUCE(-1);
-#undef BSMR_ATTN_REDUCE
-        BSMR_HIP(hipGetLastError());
-    }
-    return BSMR_OK;
+    return launchAttnReduce(bw, Kv, partial, sPart, m, O, sOut, nb, mode, s);
 }
 
 int runAttentionBackward(bsmr_backward* bw, uint32_t Kv, float scale, const float* P, const float* m, const float* sIn,

@@ -279,25 +279,31 @@ int runGather(const bsmr_backward* bw, const GatherLists& L, uint32_t K, const f
     return BSMR_OK;
 }
 
-// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.  xMode / y16 as
-// runGather.
-int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* Xrows, void* Yout, uint32_t nb, hipStream_t s,
-            int xMode = BSMR_COMPUTE_F32, bool y16 = false) {
-    const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
-    const uint64_t nnz = bw->nnz;
-    const uint64_t xB = (uint64_t)rowsX * K, yB = (uint64_t)rowsY * K, pB = (uint64_t)bw->numSlots[dir] * K;
-    float* partial = bw->work;
+// The lists of direction dir (0: rows, 1: columns) for a call with (K, nb); the workspace is already large enough.  With
+// permuteV the column direction first writes v in CSC order behind the partials of the workspace: v then points there.
+int spmmLists(bsmr_backward* bw, uint32_t K, int dir, const float*& v, uint32_t nb, hipStream_t s, GatherLists& L) {
     const uint32_t* map = dir ? bw->cscToCsr : nullptr;
-    if (dir && bw->permuteV && nnz) {   // dP in CSC order, behind the partials of the workspace
-        float* vT = bw->work + pB * nb;
+    if (dir && bw->permuteV && bw->nnz) {   // dP in CSC order, behind the partials of the workspace
+        float* vT = bw->work + (uint64_t)bw->numSlots[dir] * K * nb;
         hipLaunchKernelGGL(bsmr::spmmPermute, dim3((bw->nnz + 255u) / 256u, nb), dim3(256), 0, s, bw->cscToCsr, bw->nnz, v, vT);
         BSMR_HIP(hipGetLastError());
         v = vT;
         map = nullptr;
     }
-    const GatherLists L{bw->items[dir], bw->numItems[dir], bw->splits[dir], bw->numSplits[dir],
-                        dir ? bw->cscRows : bw->colIndices, map};
-    return runGather(bw, L, K, v, Xrows, Yout, partial, nnz, xB, yB, pB, nb, s, xMode, y16);
+    L = GatherLists{bw->items[dir], bw->numItems[dir], bw->splits[dir], bw->numSplits[dir],
+                    dir ? bw->cscRows : bw->colIndices, map};
+    return BSMR_OK;
+}
+
+// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.  xMode / y16 as
+// runGather.
+int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* Xrows, void* Yout, uint32_t nb, hipStream_t s,
+            int xMode = BSMR_COMPUTE_F32, bool y16 = false) {
+    const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
+    const uint64_t xB = (uint64_t)rowsX * K, yB = (uint64_t)rowsY * K, pB = (uint64_t)bw->numSlots[dir] * K;
+    GatherLists L;
+    if (int st = spmmLists(bw, K, dir, v, nb, s, L)) return st;
+    return runGather(bw, L, K, v, Xrows, Yout, bw->work, bw->nnz, xB, yB, pB, nb, s, xMode, y16);
 }
 
 }  // namespace

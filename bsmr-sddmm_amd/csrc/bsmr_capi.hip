@@ -2759,23 +2759,10 @@ int bsmr_sddmm_lowp(bsmr_plan* plan, uint32_t K, const void* A16, const void* B1
     return launchSparse(plan, K, A, B, P, s);
 }
 
-// The forward on 16-bit operands alone: every engine's 16-bit kernel (launchDense16) and the 16-bit residue kernel
-// (launchSparse16), whatever the plan says about the road its fp32 operands take.  Both read formats that do not
-// depend on that road: the GEMM and sweep formats are keyed by their shape alone (the fp32-operand GEMM kernels are
-// built for a subset of the 16-bit kernels' shapes) and size their LDS per launch from the operand type; a plan that
-// rounds in the streaming kernel keeps the streaming format launchStream reads; the tiles engine is only prepared
-// (prepareDense) where launchDense16 selects it; the residue lists are the same for both of its kernels.
-int bsmr_sddmm_16(bsmr_plan* plan, uint32_t K, const void* A16, const void* B16, float* P, uint32_t num_batches, int mode,
-                  void* stream) {
-    if (!plan) return BSMR_ERR_INVALID_ARG;
-    if (K == 0 || (K & 31u)) return BSMR_ERR_UNSUPPORTED_K;
-    if (mode != BSMR_COMPUTE_F16 && mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
-    plan = servedFor(plan, K, mode);
-    const bool reads = plan->nnz != 0;   // nnz = 0: nothing is read or written
-    if ((reads && (!A16 || !B16 || !P)) || !aligned16(A16) || !aligned16(B16) || !aligned4(P)) return BSMR_ERR_INVALID_ARG;
-    if (num_batches == 0 || !reads) return BSMR_OK;
-    if (num_batches > 65535u || (uint64_t)K * num_batches > 0xFFFFFFFFull) return BSMR_ERR_INVALID_ARG;
-    BSMR_HIP(hipSetDevice(plan->device));
+// The body of bsmr_sddmm_16 behind its checks (plan: the served plan, its device current; num_batches >= 1): shared with
+// bsmr_sddmm_b8 (csrc/fp8_capi.hpp), which hands it the plan's own widened copy of B.
+static int runSddmm16(bsmr_plan* plan, uint32_t K, const void* A16, const void* B16, float* P, uint32_t num_batches, int mode,
+                      void* stream) {
     const Queue s(static_cast<hipStream_t>(stream), bsmr::Batch{(uint64_t)plan->M * K, (uint64_t)plan->N * K, plan->nnz, num_batches});
     if (int st = prepareDense(plan, K, mode)) return st;
     const uint16_t* a = static_cast<const uint16_t*>(A16);
@@ -2801,6 +2788,26 @@ int bsmr_sddmm_16(bsmr_plan* plan, uint32_t K, const void* A16, const void* B16,
     }
     if (hasDense && (st = runDense(s)) != BSMR_OK) return st;
     return runSparse(s);
+}
+
+// The forward on 16-bit operands alone: every engine's 16-bit kernel (launchDense16) and the 16-bit residue kernel
+// (launchSparse16), whatever the plan says about the road its fp32 operands take.  Both read formats that do not
+// depend on that road: the GEMM and sweep formats are keyed by their shape alone (the fp32-operand GEMM kernels are
+// built for a subset of the 16-bit kernels' shapes) and size their LDS per launch from the operand type; a plan that
+// rounds in the streaming kernel keeps the streaming format launchStream reads; the tiles engine is only prepared
+// (prepareDense) where launchDense16 selects it; the residue lists are the same for both of its kernels.
+int bsmr_sddmm_16(bsmr_plan* plan, uint32_t K, const void* A16, const void* B16, float* P, uint32_t num_batches, int mode,
+                  void* stream) {
+    if (!plan) return BSMR_ERR_INVALID_ARG;
+    if (K == 0 || (K & 31u)) return BSMR_ERR_UNSUPPORTED_K;
+    if (mode != BSMR_COMPUTE_F16 && mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
+    plan = servedFor(plan, K, mode);
+    const bool reads = plan->nnz != 0;   // nnz = 0: nothing is read or written
+    if ((reads && (!A16 || !B16 || !P)) || !aligned16(A16) || !aligned16(B16) || !aligned4(P)) return BSMR_ERR_INVALID_ARG;
+    if (num_batches == 0 || !reads) return BSMR_OK;
+    if (num_batches > 65535u || (uint64_t)K * num_batches > 0xFFFFFFFFull) return BSMR_ERR_INVALID_ARG;
+    BSMR_HIP(hipSetDevice(plan->device));
+    return runSddmm16(plan, K, A16, B16, P, num_batches, mode, stream);
 }
 
 int bsmr_sddmm_timed(bsmr_plan* plan, uint32_t K, const float* A, const float* B, float* P, int mode,
@@ -3678,3 +3685,4 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
 #include "blocked_capi.hpp"
 #include "softmax_capi.hpp"
 #include "attention_capi.hpp"
+#include "fp8_capi.hpp"

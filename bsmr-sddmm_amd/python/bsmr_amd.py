@@ -21,6 +21,7 @@ LIB_DIR = PKG_DIR / "lib"
 OK = 0
 ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED_K, ERR_OOM, ERR_BAD_PLAN = 1, 2, 3, 4, 5, 6
 COMPUTE_F16, COMPUTE_BF16, COMPUTE_F32 = 0, 1, 2
+FP8_E4M3, FP8_E5M2 = 0, 1   # BSMR_FP8_*: OCP e4m3fn / e5m2, the formats of an fp8 column-side operand
 ROWS_CLUSTER, ROWS_IDENTITY = 0, 1
 
 ARRAY_IDS = {
@@ -253,6 +254,13 @@ HIP_SYMBOLS = {
                                        [C.c_uint32, C.c_void_p]),
     "bsmr_sparse_attention_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
                                           [C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_widen_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_sddmm_b8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
+                                C.c_void_p]),
+    "bsmr_spmm_x8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                               C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_x8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 5 +
+                                 [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
 }
 
 HOST_SYMBOLS = {
@@ -900,3 +908,31 @@ def sparse_attention_backward(bw, Kv: int, scale: float, P_ptr: int, m_ptr: int,
         _check(hip().bsmr_sparse_attention_backward(*args, stream), "bsmr_sparse_attention_backward")
     else:
         _check(hip().bsmr_sparse_attention_backward_16(*args, mode, stream), "bsmr_sparse_attention_backward_16")
+
+
+# --- fp8 keys and values: the column-side operand as OCP fp8 bytes (fmt FP8_E4M3 / FP8_E5M2), widened exactly to the
+# 16-bit format of `mode`; each call is bit for bit its 16-bit form on the widened operand ---
+def widen_fp8(in8_ptr: int, out16_ptr: int, count: int, mode=COMPUTE_F16, fmt=FP8_E4M3, stream: int = 0):
+    """out16[i] = widen(in8[i]) for count elements: fp8 -> fp16 (mode F16) or bf16 (BF16), exact for every code"""
+    _check(hip().bsmr_widen_fp8(in8_ptr or None, out16_ptr or None, count, mode, fmt, stream), "bsmr_widen_fp8")
+
+
+def sddmm_b8(plan, K: int, A16_ptr: int, B8_ptr: int, P_ptr: int, num_batches: int = 1, mode=COMPUTE_F16, fmt=FP8_E4M3,
+             stream: int = 0):
+    """sddmm_16(A16, widen(B8)): B is widened into the plan's 16-bit workspace, A16 is read in place"""
+    _check(hip().bsmr_sddmm_b8(plan, K, A16_ptr or None, B8_ptr or None, P_ptr or None, num_batches, mode, fmt, stream),
+           "bsmr_sddmm_b8")
+
+
+def spmm_x8(bw, K: int, transpose: bool, v_ptr: int, X8_ptr: int, Y16_ptr: int, num_batches: int = 1, stream: int = 0,
+            mode=COMPUTE_F16, fmt=FP8_E4M3):
+    """Y16 = round(S_v widen(X8)) (transpose True: S_v^T): fp8 rows gathered and widened in registers, no copy"""
+    _check(hip().bsmr_spmm_x8(bw, K, int(bool(transpose)), v_ptr or None, X8_ptr or None, Y16_ptr, num_batches, mode, fmt,
+                              stream), "bsmr_spmm_x8")
+
+
+def sparse_attention_x8(bw, Kv: int, scale: float, P_ptr: int, V8_ptr: int, O16_ptr: int, m_ptr: int, s_ptr: int,
+                        num_batches: int = 1, stream: int = 0, mode=COMPUTE_F16, fmt=FP8_E4M3):
+    """sparse_attention on fp8 rows of V: O16 (mode's format), m and s as bsmr_sparse_attention_16 on widen(V8)"""
+    _check(hip().bsmr_sparse_attention_x8(bw, Kv, scale, P_ptr or None, V8_ptr or None, O16_ptr or None, m_ptr or None,
+                                          s_ptr or None, num_batches, mode, fmt, stream), "bsmr_sparse_attention_x8")

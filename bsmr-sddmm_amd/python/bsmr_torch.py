@@ -56,6 +56,23 @@ Sums run in fp32 on the exactly widened rows and each output element is rounded 
 value tensors - `values`, P, the input and output of softmax - are fp32 only: scores and weights are never 16-bit.
 fp32 operands take the fp32 calls, bit for bit as before.
 
+fp8 keys and values.  The column-side operand - B / Kt of sddmm, X / V of spmm, softmax_spmm and attention - may be
+torch.float8_e4m3fn or torch.float8_e5m2, as an fp8 KV cache holds it (include/bsmr_hip.h "fp8 keys and values").  Both
+formats embed exactly in fp16 and in bf16, so every such call is, bit for bit, the 16-bit call on the exactly widened
+tensor - and nothing is cast or copied by the operator:
+    sddmm(A, B8):  A fp16 / bf16 -> P (fp32) = bsmr_sddmm_b8 (B8 is widened into the plan's workspace, A read in place);
+                   dA in A's dtype = bsmr_spmm_x8(dP, B8)
+    spmm(values, X8, out_dtype=torch.float16 | torch.bfloat16):  Y in out_dtype = bsmr_spmm_x8, the gather reading the
+                   bytes;  d values = bsmr_sddmm_b8(dY, X8).  transpose=True is refused (an fp8 row-side operand)
+    softmax_spmm(values, X8, scale, out_dtype=...):  bsmr_sparse_attention_x8, saving (values, X8, m, s, O);
+                   dW = bsmr_sddmm_b8(dO, X8), then bsmr_sparse_attention_backward_16 on (O, dO)
+    attention(Q, Kt, V):  Kt and V may each be fp8, independently; out_dtype (default Q.dtype) is used when V is fp8
+No gradient flows into an fp8 tensor: one that requires grad raises ValueError at the call.  out_dtype belongs to fp8 X
+alone (ValueError with any other X, and when it is missing or not a 16-bit dtype with an fp8 X).  On a blocked=True
+operator an fp8 X takes the gather: the blocked SpMM has no fp8 form, as it has none for the transposed direction.
+Out of scope: scale factors (a per-tensor scale of K folds into `scale` and one of V into the output, by the caller;
+per-row and MX block scales are later work), fp8 on the MFMA of the dense engine, fp8 outputs, an fp8 row-side operand.
+
 Every call runs on torch.cuda.current_stream(device).  Operands are contiguous, on the operator's device, with
 K a positive multiple of 32; anything else raises ValueError.  Double backward is not supported.  Calls on one operator
 share its workspaces: issue them from one thread (the current stream orders them).
@@ -71,6 +88,11 @@ import bsmr_amd as eng
 
 
 _MODE16 = {torch.float16: eng.COMPUTE_F16, torch.bfloat16: eng.COMPUTE_BF16}   # the format follows the dtype
+_MODE8 = {torch.float8_e4m3fn: eng.FP8_E4M3, torch.float8_e5m2: eng.FP8_E5M2}
+
+
+def _is8(t) -> bool:
+    return isinstance(t, torch.Tensor) and t.dtype in _MODE8
 
 
 class SparseOperator:
@@ -111,12 +133,19 @@ class SparseOperator:
 
     # --- public operators ---
     def sddmm(self, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
-        """P = (A B^T) at S's stored positions: A (M,K) / B (N,K), or (b,M,K) / (b,N,K); P (nnz,) or (b,nnz)"""
+        """P = (A B^T) at S's stored positions: A (M,K) / B (N,K), or (b,M,K) / (b,N,K); P (nnz,) or (b,nnz).
+        B may be fp8 (e4m3fn / e5m2) beside an fp16 / bf16 A: no gradient reaches it."""
+        if _is8(B):
+            self._no_grad8(B, "B")
+            return _SDDMM8.apply(self, A, B)
         return _SDDMM.apply(self, A, B)
 
-    def spmm(self, values: torch.Tensor, X: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    def spmm(self, values: torch.Tensor, X: torch.Tensor, transpose: bool = False, out_dtype=None) -> torch.Tensor:
         """Y = S_values X (X (N,K) -> Y (M,K)) or, transposed, S_values^T X (X (M,K) -> Y (N,K)); batched with a
-        leading b on values (b,nnz) and X"""
+        leading b on values (b,nnz) and X.  fp8 X: out_dtype (torch.float16 or torch.bfloat16) is Y's dtype and
+        transpose must be False; on a blocked=True operator it takes the gather (the blocked SpMM has no fp8 form)."""
+        if self._fp8_call(X, transpose, out_dtype):
+            return _SpMM8.apply(self, values, X, out_dtype)
         return _SpMM.apply(self, values, X, bool(transpose))
 
     def softmax(self, values: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
@@ -124,22 +153,27 @@ class SparseOperator:
         entries are all -inf gives zeros, a NaN or +inf makes its row NaN, rows without entries hold nothing"""
         return _Softmax.apply(self, values, scale)
 
-    def softmax_spmm(self, values: torch.Tensor, X: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    def softmax_spmm(self, values: torch.Tensor, X: torch.Tensor, scale: float = 1.0, out_dtype=None) -> torch.Tensor:
         """spmm(softmax(values, scale), X) in one gather (bsmr_sparse_attention): values (nnz,) or (b, nnz) fp32, X (N, K)
         or (b, N, K) in fp32, fp16 or bf16 -> Y (M, K) in X's dtype.  A row of S without entries, or whose entries are
-        all -inf, gives a zero row; a NaN or +inf makes its row NaN."""
+        all -inf, gives a zero row; a NaN or +inf makes its row NaN.  fp8 X: Y in out_dtype, the rule of spmm."""
+        if self._fp8_call(X, False, out_dtype):
+            return _SoftmaxSpMM8.apply(self, values, X, scale, out_dtype)
         return _SoftmaxSpMM.apply(self, values, X, scale)
 
-    def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None, fused: bool = False) -> torch.Tensor:
+    def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None, fused: bool = False,
+                  out_dtype=None) -> torch.Tensor:
         """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
         positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row.
-        fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order."""
+        fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order.
+        Kt and V may each be fp8; out_dtype (default Q.dtype) is the result's dtype when V is fp8, unused otherwise."""
         P = self.sddmm(Q, Kt)
         if scale is None:
             scale = Q.shape[-1] ** -0.5
+        out_dtype = (Q.dtype if out_dtype is None else out_dtype) if _is8(V) else None
         if fused:
-            return self.softmax_spmm(P, V, scale)
-        return self.spmm(self.softmax(P, scale), V)
+            return self.softmax_spmm(P, V, scale, out_dtype=out_dtype)
+        return self.spmm(self.softmax(P, scale), V, out_dtype=out_dtype)
 
     def stats(self) -> dict:
         return eng.backward_stats(self._bw)
@@ -148,11 +182,32 @@ class SparseOperator:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _check(self, t: torch.Tensor, name: str, rows: int, batch):
-        """batch None: either (rows, K) or (b, rows, K); returns (b or None, K)"""
+    @staticmethod
+    def _no_grad8(t: torch.Tensor, name: str):
+        if t.requires_grad:
+            raise ValueError(f"{name}: an fp8 tensor that requires grad - no gradient is computed into fp8 operands")
+
+    def _fp8_call(self, X, transpose, out_dtype) -> bool:
+        """whether a call with X and out_dtype is the fp8 form; raises on the combinations neither form accepts"""
+        if not _is8(X):
+            if out_dtype is not None:
+                raise ValueError("out_dtype: only an fp8 X takes it, every other X gives its own dtype")
+            return False
+        if out_dtype not in _MODE16:
+            raise ValueError(f"out_dtype: {out_dtype!r}, an fp8 X needs torch.float16 or torch.bfloat16")
+        if transpose:
+            raise ValueError("transpose=True with an fp8 X: the row-side operand is never fp8")
+        self._no_grad8(X, "X")
+        return True
+
+    def _check(self, t: torch.Tensor, name: str, rows: int, batch, fp8: bool = False):
+        """batch None: either (rows, K) or (b, rows, K); returns (b or None, K).  fp8: the tensor must be fp8"""
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name}: expected a torch.Tensor")
-        if t.dtype != torch.float32 and t.dtype not in _MODE16:
+        if fp8:
+            if t.dtype not in _MODE8:
+                raise ValueError(f"{name}: dtype {t.dtype}, expected torch.float8_e4m3fn or torch.float8_e5m2")
+        elif t.dtype != torch.float32 and t.dtype not in _MODE16:
             raise ValueError(f"{name}: dtype {t.dtype}, expected torch.float32, torch.float16 or torch.bfloat16")
         if t.device != self.device:
             raise ValueError(f"{name}: on {t.device}, the operator lives on {self.device}")
@@ -222,6 +277,41 @@ class SparseOperator:
         eng.spmm(self._bw, K, transpose, v.data_ptr(), X.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
                  mode=self.gather_mode)
         return Y
+
+    # --- fp8 column-side operand: the 16-bit calls on the exactly widened tensor, nothing cast or copied ---
+    def _sddmm_b8(self, A: torch.Tensor, B8: torch.Tensor) -> torch.Tensor:
+        b, K = self._check(A, "A", self.M, None)
+        _, K2 = self._check(B8, "B", self.N, (b,), fp8=True)
+        if A.dtype not in _MODE16:
+            raise ValueError(f"A: dtype {A.dtype} beside an fp8 B, expected torch.float16 or torch.bfloat16")
+        if K2 != K:
+            raise ValueError(f"A and B disagree on K ({K} vs {K2})")
+        P = torch.empty((self.nnz,) if b is None else (b, self.nnz), dtype=torch.float32, device=self.device)
+        if self.nnz:
+            eng.sddmm_b8(self._plan, K, A.data_ptr(), B8.data_ptr(), P.data_ptr(), b or 1, _MODE16[A.dtype],
+                         _MODE8[B8.dtype], self._stream())
+        return P
+
+    def _spmm_x8(self, v: torch.Tensor, X8: torch.Tensor, out_dtype) -> torch.Tensor:
+        """Y (M, K) in out_dtype; the gather also on a blocked operator"""
+        b, K = self._check(X8, "X", self.N, None, fp8=True)
+        self._check_values(v, b)
+        Y = torch.empty((self.M, K) if b is None else (b, self.M, K), dtype=out_dtype, device=self.device)
+        eng.spmm_x8(self._bw, K, False, v.data_ptr(), X8.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
+                    mode=_MODE16[out_dtype], fmt=_MODE8[X8.dtype])
+        return Y
+
+    def _attention_x8(self, v: torch.Tensor, X8: torch.Tensor, scale, out_dtype):
+        """_attention on fp8 rows: O in out_dtype"""
+        b, K = self._check(X8, "X", self.N, None, fp8=True)
+        _, scale = self._softmax_args(v, scale)
+        self._check_values(v, b)
+        O = torch.empty((self.M, K) if b is None else (b, self.M, K), dtype=out_dtype, device=self.device)
+        m = torch.empty((self.M,) if b is None else (b, self.M), dtype=torch.float32, device=self.device)
+        s = torch.empty_like(m)
+        eng.sparse_attention_x8(self._bw, K, scale, v.data_ptr(), X8.data_ptr(), O.data_ptr(), m.data_ptr(), s.data_ptr(),
+                                b or 1, self._stream(), mode=_MODE16[out_dtype], fmt=_MODE8[X8.dtype])
+        return O, m, s
 
     def _softmax_args(self, v: torch.Tensor, scale):
         if not isinstance(v, torch.Tensor):
@@ -329,6 +419,40 @@ class _SDDMM(torch.autograd.Function):
         return None, dA, dB
 
 
+class _SDDMM8(torch.autograd.Function):
+    """sddmm with an fp8 B: dA = S_dP widen(B8) in A's dtype, nothing into B"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, A, B8):
+        ctx.op = op
+        ctx.save_for_backward(A, B8)
+        return op._sddmm_b8(A, B8)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dP):
+        A, B8 = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None
+        return None, ctx.op._spmm_x8(_grad(dP), B8, A.dtype), None
+
+
+class _SpMM8(torch.autograd.Function):
+    """spmm with an fp8 X: d values = sddmm(dY, widen(X8)), nothing into X"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, values, X8, out_dtype):
+        ctx.op, ctx.out_dtype = op, out_dtype
+        ctx.save_for_backward(X8)
+        return op._spmm_x8(values, X8, out_dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dY):
+        (X8,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        return None, ctx.op._sddmm_b8(_grad(dY, ctx.out_dtype), X8), None, None
+
+
 class _SpMM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, op: SparseOperator, values, X, transpose: bool):
@@ -387,6 +511,27 @@ class _SoftmaxSpMM(torch.autograd.Function):
         dP, W = op._attention_backward(values, m, s, op._sddmm(dO, X), O, dO, ctx.scale)
         dX = op._spmm(W, dO, True) if need_x else None
         return None, dP if need_v else None, dX, None
+
+
+class _SoftmaxSpMM8(torch.autograd.Function):
+    """softmax_spmm with an fp8 X: the backward of _SoftmaxSpMM without dX"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, values, X8, scale, out_dtype):
+        O, m, s = op._attention_x8(values, X8, scale, out_dtype)
+        ctx.op, ctx.scale = op, float(scale)
+        ctx.save_for_backward(values, X8, m, s, O)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        op = ctx.op
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        values, X8, m, s, O = ctx.saved_tensors
+        dO = _grad(dO, O.dtype)
+        dP, _ = op._attention_backward(values, m, s, op._sddmm_b8(dO, X8), O, dO, ctx.scale)
+        return None, dP, None, None, None
 
 
 __all__ = ["SparseOperator"]

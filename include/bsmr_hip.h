@@ -742,6 +742,48 @@ int bsmr_sparse_attention_backward_16(bsmr_backward *bw, uint32_t Kv, float scal
                                       const void *dO16_dev, float *dP_dev, float *W_dev, uint32_t num_batches,
                                       int compute_mode, void *stream);
 
+/* ---- fp8 keys and values (revision 5, added without any layout change; no reference counterpart) ----
+ * The column-side operand - B / Kt of the SDDMM, X / V of the SpMM and of the fused attention - may be OCP fp8, one byte per
+ * element, as an fp8 KV cache holds it: fp8_format BSMR_FP8_E4M3 (e4m3fn: no infinity, two NaN codes) or BSMR_FP8_E5M2 (two
+ * infinities, six NaN codes).  The row-side operand (A / Q) and the outputs (Y, O) are fp16 or bf16: compute_mode is
+ * BSMR_COMPUTE_F16 or BSMR_COMPUTE_BF16, the format of every 16-bit array of the call and the format the fp8 operand is
+ * widened to; BSMR_COMPUTE_F32 or any other value is BSMR_ERR_INVALID_ARG, and so is an fp8_format outside {0, 1}.  P, v, m,
+ * s and every sum stay fp32.  The fp8 format is an argument of these functions alone: the _mode, _lowp and _16 entry points
+ * accept the compute modes they accepted before.
+ *
+ * Numerical contract.  Every code of both formats is a value of fp16 and of bf16, so widening is exact: +-0 keeps its
+ * sign, subnormals widen exactly, e5m2 +-inf stays +-inf, every NaN code becomes a NaN.  An fp8 call is, bit for bit, the
+ * 16-bit call on the widened operand:
+ *   bsmr_widen_fp8(in8, out16, count)     out16[i] = widen(in8[i]) in compute_mode's format; count elements, any count
+ *   bsmr_sddmm_b8(A16, B8)             == bsmr_sddmm_16(A16, widen(B8))
+ *   bsmr_spmm_x8(v, X8)                == bsmr_spmm_16(v, widen(X8))              both directions
+ *   bsmr_sparse_attention_x8(P, V8)    == bsmr_sparse_attention_16(P, widen(V8))  O16, m and s
+ * with the reproducibility of those calls.  No scale factor is applied: a per-tensor scale of K folds into the attention
+ * scale and one of V into the output, by the caller.
+ *
+ * bsmr_sddmm_b8 widens B8 ([b][N][K] bytes) into the plan's 16-bit workspace on the call's stream - the workspace of
+ * bsmr_sddmm_batch for K * num_batches, allocated on the first call that needs it - and runs bsmr_sddmm_16 on (A16, that
+ * copy); A16 is read in place.  bsmr_spmm_x8 and bsmr_sparse_attention_x8 make no copy: the gathers of their _16 forms
+ * read the bytes (rows of K bytes, row and batch offsets formed in 64 bits) and widen in registers.  Same lists, chunks and
+ * fma chains; fp32 chunk partials in the workspace that bsmr_backward_reserve / bsmr_sparse_attention_reserve size; one
+ * rounding per output element.  The backward of the fused attention is bsmr_sparse_attention_backward_16 on (O16, dO16).
+ *
+ * Checked before any device work, in the order of the _16 forms: a NULL plan / handle or a non-finite scale
+ * (BSMR_ERR_INVALID_ARG), K = 0 or not a multiple of 32 (BSMR_ERR_UNSUPPORTED_K), compute_mode and fp8_format, then the
+ * pointers - 16 bytes for the fp8 and the 16-bit arrays, 4 for P, v, m and s - and more than 65535 batches.  num_batches =
+ * 0 is a no-op; with nnz = 0 the inputs may be NULL and nothing is read.  bsmr_widen_fp8: count = 0 is a no-op whatever
+ * the pointers; otherwise both must be non-NULL and 16-byte aligned.  It runs on the current device. */
+#define BSMR_FP8_E4M3 0   /* OCP e4m3fn (torch.float8_e4m3fn) */
+#define BSMR_FP8_E5M2 1   /* OCP e5m2   (torch.float8_e5m2)   */
+int bsmr_widen_fp8(const void *in8_dev, void *out16_dev, uint64_t count, int compute_mode, int fp8_format, void *stream);
+int bsmr_sddmm_b8(bsmr_plan *plan, uint32_t K, const void *A16_dev, const void *B8_dev, float *P_dev,
+                  uint32_t num_batches, int compute_mode, int fp8_format, void *stream);
+int bsmr_spmm_x8(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const void *X8_dev, void *Y16_dev,
+                 uint32_t num_batches, int compute_mode, int fp8_format, void *stream);
+int bsmr_sparse_attention_x8(bsmr_backward *bw, uint32_t Kv, float scale, const float *P_dev, const void *V8_dev,
+                             void *O16_dev, float *m_dev, float *s_dev, uint32_t num_batches, int compute_mode,
+                             int fp8_format, void *stream);
+
 /* ---- Blocked SpMM: Y = S_v X over the RPHM's dense 16 x 16 blocks (revision 5, added without any layout change) ----
  * The row direction of bsmr_spmm with the dense part of the reordering put to use: in a row panel the 16 columns of a
  * dense block are shared by 16 output rows, so a row of X is read once per block instead of once per stored entry and the
