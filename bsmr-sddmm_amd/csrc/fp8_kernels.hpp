@@ -12,6 +12,13 @@
 //                 chunk partials in the workspace (spmmReduce16 adds and rounds them), one rounding per output element
 //   attnGather8   attnGather16 with the same substitution; attnRowMax and attnReduce are reused as they are
 //
+// MX block scales: one E8M0 byte per 32 consecutive elements of a row, E[b][rows][K/32]; code e is
+// 2^(e-127), 255 is NaN.  dq = widen(code) * scale is one fp32 multiplication (subnormal products kept, overflow to
+// +-inf) in front of the fma chain.  widenFp8Mx and the MX = true instantiations of the gathers are the kernels above
+// with that one multiplication (MX = false compiles the scale away, E is then never read), so lists, chunks, rows in
+// flight, lane layout, partials and reduce kernels are the same.  A lane's VE bytes lie in one block of 32, so it loads
+// one scale byte per source row, at E + s * (K / 32) + col / 32.
+//
 // Lane layout: VE source bytes per lane - 16 (one 16-byte load) for the slice widths 256 and 128, 8 (one 8-byte load)
 // for 64 and 32 - so G = W / VE = 16, 8, 8, 4 lanes per unit and 4, 8, 8, 16 units per wave.  No sum is split across
 // lanes: the layout cannot change a bit.  A lane's load starts VE bytes into a slice that starts W bytes into a row of K
@@ -56,6 +63,38 @@ __device__ __forceinline__ void bwFma8(float w, const BwBytes<VE>& x, float (&ac
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[4 * i + k] = fmaf(w, e[k], acc[4 * i + k]);
     }
+}
+
+// 2^(e - 127) for an E8M0 code, built from bits: 1 .. 254 are the exponent field of a normal, 0 is the subnormal
+// 2^-127, 255 a quiet NaN
+__device__ __forceinline__ float bwScaleMx(uint32_t e) {
+    return __uint_as_float(e == 0u ? 0x00400000u : e == 255u ? 0x7FC00000u : e << 23);
+}
+
+// bwFma8 on dq = widen(code) * sc: the element is dequantised by one fp32 multiplication, then enters the chain
+template <int FMT, int VE>
+__device__ __forceinline__ void bwFma8Mx(float w, const BwBytes<VE>& x, float sc, float (&acc)[VE]) {
+#pragma unroll
+    for (int i = 0; i < VE / 4; ++i) {
+        float e[4];
+        bwWiden8<FMT>(x[i], e);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[4 * i + k] = fmaf(w, e[k] * sc, acc[4 * i + k]);
+    }
+}
+
+// the scale code of source row s for a lane whose block column es points at (KB = K / 32 bytes per row)
+template <bool MX>
+__device__ __forceinline__ uint32_t bwScaleByte(const uint8_t* es, uint32_t s, uint32_t KB) {
+    if constexpr (MX) return es[(uint64_t)s * KB];
+    else return 0u;
+}
+
+// one source row's term of a lane: the row's bytes x, its scale code e (MX)
+template <int FMT, int VE, bool MX>
+__device__ __forceinline__ void bwRowFma8(float w, const BwBytes<VE>& x, uint32_t e, float (&acc)[VE]) {
+    if constexpr (MX) bwFma8Mx<FMT, VE>(w, x, bwScaleMx(e), acc);
+    else bwFma8<FMT, VE>(w, x, acc);
 }
 
 // VE fp32 sums of a finished row, rounded once to MODE's format: 16 bytes per store
@@ -104,15 +143,39 @@ widenFp8(const uint8_t* __restrict__ in, uint16_t* __restrict__ out, uint64_t co
     }
 }
 
+// out[i] = narrow(widen(in[i]) * 2^(scales[i / 32] - 127)): widenFp8 with one scale byte per group of 16 elements (group
+// i lies in block i / 2).  count is a multiple of 32, so there is no tail.
+template <int MODE, int FMT>
+__global__ void __launch_bounds__(256)
+widenFp8Mx(const uint8_t* __restrict__ in, const uint8_t* __restrict__ scales, uint16_t* __restrict__ out, uint64_t count) {
+    const uint64_t n16 = count / 16u, stride = (uint64_t)gridDim.x * 256u;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n16; i += stride) {
+        const u32x4 w = reinterpret_cast<const u32x4*>(in)[i];
+        const float sc = bwScaleMx(scales[i / 2u]);
+        float x[16];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float e[4];
+            bwWiden8<FMT>(w[c], e);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[4 * c + k] = e[k] * sc;
+        }
+        bwStoreNarrow<MODE, 16>(out + i * 16u, x);
+    }
+}
+
 // W: slice width in elements; VE: source bytes per lane; G = W / VE lanes per unit, 64 / G units per wave.  MAP: v is
 // read through map[t].  v, the accumulators and the partials are fp32; Y holds MODE's 16-bit format: an item that owns
 // its whole list rounds its sums and stores them, a chunk of a split list writes its fp32 partial.
-template <int W, int VE, bool MAP, int MODE, int FMT>
+// MX: the gather runs on dq(X, E) - every widened element is multiplied by its block's scale, read from E ([b][rows][K / 32]
+// bytes, batch stride eBatch).  Without MX (the default: bsmr_spmm_x8) the two last arguments are never read and the
+// instantiation is, instruction for instruction, the kernel it was before they existed.
+template <int W, int VE, bool MAP, int MODE, int FMT, bool MX = false>
 __global__ void __launch_bounds__(256)
 spmmGather8(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSlices, const uint32_t* __restrict__ src,
             const uint32_t* __restrict__ map, const float* __restrict__ v, const uint8_t* __restrict__ X,
             uint16_t* __restrict__ Y, float* __restrict__ partial, uint32_t K, uint64_t vBatch, uint64_t xBatch,
-            uint64_t yBatch, uint64_t pBatch) {
+            uint64_t yBatch, uint64_t pBatch, const uint8_t* __restrict__ E, uint64_t eBatch) {
     constexpr int G = W / VE;
     constexpr int UPW = 64 / G;   // units per wave
     static_assert(G >= 4 && G <= 64 && (VE == 8 || VE == 16), "lane layout");
@@ -125,6 +188,8 @@ spmmGather8(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSli
     const uint64_t b = blockIdx.y;
     const uint64_t col = (uint64_t)slice * W + (uint64_t)gl * VE;
     const uint8_t* xs = X + b * xBatch + col;
+    const uint8_t* es = MX ? E + b * eBatch + col / 32u : nullptr;
+    const uint32_t KB = K / 32u;
     const float* vb = v + b * vBatch;
     float acc[VE];
 #pragma unroll
@@ -149,15 +214,17 @@ spmmGather8(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSli
             const T x1 = *reinterpret_cast<const T*>(xs + (uint64_t)s1 * K);
             const T x2 = *reinterpret_cast<const T*>(xs + (uint64_t)s2 * K);
             const T x3 = *reinterpret_cast<const T*>(xs + (uint64_t)s3 * K);
-            bwFma8<FMT, VE>(w0, x0, acc);
-            bwFma8<FMT, VE>(w1, x1, acc);
-            bwFma8<FMT, VE>(w2, x2, acc);
-            bwFma8<FMT, VE>(w3, x3, acc);
+            const uint32_t e0 = bwScaleByte<MX>(es, s0, KB), e1 = bwScaleByte<MX>(es, s1, KB);
+            const uint32_t e2 = bwScaleByte<MX>(es, s2, KB), e3 = bwScaleByte<MX>(es, s3, KB);
+            bwRowFma8<FMT, VE, MX>(w0, x0, e0, acc);
+            bwRowFma8<FMT, VE, MX>(w1, x1, e1, acc);
+            bwRowFma8<FMT, VE, MX>(w2, x2, e2, acc);
+            bwRowFma8<FMT, VE, MX>(w3, x3, e3, acc);
         }
         for (; j < n; ++j) {
             const uint32_t sj = bwBroadcast<G>(s, groupBase, j);
             const float wj = __uint_as_float(bwBroadcast<G>(w, groupBase, j));
-            bwFma8<FMT, VE>(wj, *reinterpret_cast<const T*>(xs + (uint64_t)sj * K), acc);
+            bwRowFma8<FMT, VE, MX>(wj, *reinterpret_cast<const T*>(xs + (uint64_t)sj * K), bwScaleByte<MX>(es, sj, KB), acc);
         }
     }
     if (item.slot == kBwDirect)   // the one store of a finished row
@@ -168,12 +235,14 @@ spmmGather8(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSli
 
 // attnGather16 over fp8 rows of V, O in MODE's 16-bit format: a direct item rounds its quotients once and stores them, a
 // chunk item writes its fp32 partial row and partial sum.
-template <int W, int VE, int MODE, int FMT>
+// MX: on dq(V, E), as in spmmGather8; the sum of the weights does not see the scales.
+template <int W, int VE, int MODE, int FMT, bool MX = false>
 __global__ void __launch_bounds__(256)
 attnGather8(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSlices, const uint32_t* __restrict__ src,
             float scale, const float* __restrict__ p, const float* __restrict__ m, const uint8_t* __restrict__ X,
             uint16_t* __restrict__ O, float* __restrict__ sOut, float* __restrict__ partial, float* __restrict__ sPart,
-            uint32_t K, uint32_t M, uint32_t numSlots, uint64_t nnz, uint64_t xBatch) {
+            uint32_t K, uint32_t M, uint32_t numSlots, uint64_t nnz, uint64_t xBatch, const uint8_t* __restrict__ E,
+            uint64_t eBatch) {
 #pragma clang fp contract(off)
     constexpr int G = W / VE;
     constexpr int UPW = 64 / G;   // units per wave
@@ -187,6 +256,8 @@ attnGather8(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSli
     const uint64_t b = blockIdx.y;
     const uint64_t col = (uint64_t)slice * W + (uint64_t)gl * VE;
     const uint8_t* xs = X + b * xBatch + col;
+    const uint8_t* es = MX ? E + b * eBatch + col / 32u : nullptr;
+    const uint32_t KB = K / 32u;
     const float* pb = p + b * nnz;
     const float mr = m[b * M + item.dest];
     float acc[VE];
@@ -213,20 +284,22 @@ attnGather8(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSli
             const T x1 = *reinterpret_cast<const T*>(xs + (uint64_t)s1 * K);
             const T x2 = *reinterpret_cast<const T*>(xs + (uint64_t)s2 * K);
             const T x3 = *reinterpret_cast<const T*>(xs + (uint64_t)s3 * K);
+            const uint32_t e0 = bwScaleByte<MX>(es, s0, KB), e1 = bwScaleByte<MX>(es, s1, KB);
+            const uint32_t e2 = bwScaleByte<MX>(es, s2, KB), e3 = bwScaleByte<MX>(es, s3, KB);
             sum = sum + w0;
             sum = sum + w1;
             sum = sum + w2;
             sum = sum + w3;
-            bwFma8<FMT, VE>(w0, x0, acc);
-            bwFma8<FMT, VE>(w1, x1, acc);
-            bwFma8<FMT, VE>(w2, x2, acc);
-            bwFma8<FMT, VE>(w3, x3, acc);
+            bwRowFma8<FMT, VE, MX>(w0, x0, e0, acc);
+            bwRowFma8<FMT, VE, MX>(w1, x1, e1, acc);
+            bwRowFma8<FMT, VE, MX>(w2, x2, e2, acc);
+            bwRowFma8<FMT, VE, MX>(w3, x3, e3, acc);
         }
         for (; j < n; ++j) {
             const uint32_t sj = bwBroadcast<G>(s, groupBase, j);
             const float wj = __uint_as_float(bwBroadcast<G>(w, groupBase, j));
             sum = sum + wj;
-            bwFma8<FMT, VE>(wj, *reinterpret_cast<const T*>(xs + (uint64_t)sj * K), acc);
+            bwRowFma8<FMT, VE, MX>(wj, *reinterpret_cast<const T*>(xs + (uint64_t)sj * K), bwScaleByte<MX>(es, sj, KB), acc);
         }
     }
     if (item.slot == kBwDirect) {   // the one store of a finished row

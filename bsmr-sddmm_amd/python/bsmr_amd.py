@@ -261,6 +261,13 @@ HIP_SYMBOLS = {
                                C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_x8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 5 +
                                  [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_widen_fp8_mx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_sddmm_b8_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                   C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_spmm_x8_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_x8_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
+                                    [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
 }
 
 HOST_SYMBOLS = {
@@ -936,3 +943,33 @@ def sparse_attention_x8(bw, Kv: int, scale: float, P_ptr: int, V8_ptr: int, O16_
     """sparse_attention on fp8 rows of V: O16 (mode's format), m and s as bsmr_sparse_attention_16 on widen(V8)"""
     _check(hip().bsmr_sparse_attention_x8(bw, Kv, scale, P_ptr or None, V8_ptr or None, O16_ptr or None, m_ptr or None,
                                           s_ptr or None, num_batches, mode, fmt, stream), "bsmr_sparse_attention_x8")
+
+
+# --- MX block scales on the fp8 operand (MXFP8): `scales` is [b][rows][K/32] E8M0 bytes, code e = 2^(e-127), 255 NaN;
+# dq = widen(code) * scale is one fp32 multiplication in front of everything else (include/bsmr_hip.h "MX block scales") ---
+def widen_fp8_mx(in8_ptr: int, scales_ptr: int, out16_ptr: int, count: int, mode=COMPUTE_F16, fmt=FP8_E4M3, stream: int = 0):
+    """out16[i] = narrow(widen(in8[i]) * 2^(scales[i / 32] - 127)); count a multiple of 32"""
+    _check(hip().bsmr_widen_fp8_mx(in8_ptr or None, scales_ptr or None, out16_ptr or None, count, mode, fmt, stream),
+           "bsmr_widen_fp8_mx")
+
+
+def sddmm_b8_mx(plan, K: int, A16_ptr: int, B8_ptr: int, Bs_ptr: int, P_ptr: int, num_batches: int = 1, mode=COMPUTE_F16,
+                fmt=FP8_E4M3, stream: int = 0):
+    """sddmm_16(A16, narrow(dq(B8, Bs))): B is dequantised into the plan's 16-bit workspace, A16 is read in place"""
+    _check(hip().bsmr_sddmm_b8_mx(plan, K, A16_ptr or None, B8_ptr or None, Bs_ptr or None, P_ptr or None, num_batches,
+                                  mode, fmt, stream), "bsmr_sddmm_b8_mx")
+
+
+def spmm_x8_mx(bw, K: int, transpose: bool, v_ptr: int, X8_ptr: int, Xs_ptr: int, Y16_ptr: int, num_batches: int = 1,
+               stream: int = 0, mode=COMPUTE_F16, fmt=FP8_E4M3):
+    """Y16 = round(S_v dq(X8, Xs)) (transpose True: S_v^T): the fp32 gather on the dequantised rows, no copy"""
+    _check(hip().bsmr_spmm_x8_mx(bw, K, int(bool(transpose)), v_ptr or None, X8_ptr or None, Xs_ptr or None, Y16_ptr,
+                                 num_batches, mode, fmt, stream), "bsmr_spmm_x8_mx")
+
+
+def sparse_attention_x8_mx(bw, Kv: int, scale: float, P_ptr: int, V8_ptr: int, Vs_ptr: int, O16_ptr: int, m_ptr: int,
+                           s_ptr: int, num_batches: int = 1, stream: int = 0, mode=COMPUTE_F16, fmt=FP8_E4M3):
+    """sparse_attention on dq(V8, Vs): O16 rounded once (mode's format), m and s those of the fp32 call"""
+    _check(hip().bsmr_sparse_attention_x8_mx(bw, Kv, scale, P_ptr or None, V8_ptr or None, Vs_ptr or None, O16_ptr or None,
+                                             m_ptr or None, s_ptr or None, num_batches, mode, fmt, stream),
+           "bsmr_sparse_attention_x8_mx")

@@ -70,8 +70,19 @@ tensor - and nothing is cast or copied by the operator:
 No gradient flows into an fp8 tensor: one that requires grad raises ValueError at the call.  out_dtype belongs to fp8 X
 alone (ValueError with any other X, and when it is missing or not a 16-bit dtype with an fp8 X).  On a blocked=True
 operator an fp8 X takes the gather: the blocked SpMM has no fp8 form, as it has none for the transposed direction.
-Out of scope: scale factors (a per-tensor scale of K folds into `scale` and one of V into the output, by the caller;
-per-row and MX block scales are later work), fp8 on the MFMA of the dense engine, fp8 outputs, an fp8 row-side operand.
+Out of scope: per-row fp32 scales (a per-tensor scale of K folds into `scale` and one of V into the output, a per-row
+one into values or P, by the caller), fp8 on the MFMA of the dense engine, fp8 outputs, an fp8 row-side operand.
+
+MX block scales (MXFP8).  Every fp8 operand above takes a keyword - B_scale, X_scale, Kt_scale, V_scale - with the block
+scales of the OCP Microscaling format: torch.float8_e8m0fnu or torch.uint8, shape (rows, K/32) or (b, rows, K/32) with
+the operand's batch, contiguous, on the operator's device; one E8M0 code per 32 consecutive elements of a row, code e =
+2^(e-127), 255 = NaN.  The operand is then dq = widen(code) * scale, one fp32 multiplication (include/bsmr_hip.h "MX block
+scales"), and the calls above become bsmr_sddmm_b8_mx, bsmr_spmm_x8_mx and bsmr_sparse_attention_x8_mx in the forward and
+in the backward alike; no gradient goes into codes or scales.  None (the default) is the unscaled call, the code that ran
+before.  A scale beside an operand that is not fp8, of another dtype, shape, batch or device, or one that requires grad
+raises ValueError.  bf16 is the format to put beside an MXFP8 Kt: the 16-bit copy sddmm dequantises into is exact in
+bf16 for every scale code >= 3 (e4m3) / >= 10 (e5m2), in fp16 only for shifts in [-15, 7] / [-8, 0].
+mx_quantize / mx_dequantize (plain torch, not a hot path) make and read such tensors.
 
 Every call runs on torch.cuda.current_stream(device).  Operands are contiguous, on the operator's device, with
 K a positive multiple of 32; anything else raises ValueError.  Double backward is not supported.  Calls on one operator
@@ -89,10 +100,58 @@ import bsmr_amd as eng
 
 _MODE16 = {torch.float16: eng.COMPUTE_F16, torch.bfloat16: eng.COMPUTE_BF16}   # the format follows the dtype
 _MODE8 = {torch.float8_e4m3fn: eng.FP8_E4M3, torch.float8_e5m2: eng.FP8_E5M2}
+_EMAX8 = {torch.float8_e4m3fn: 8, torch.float8_e5m2: 15}   # exponent of the largest normal: 448 = 1.75 2^8, 57344 = 1.75 2^15
+_SCALE_DTYPES = (torch.uint8,) + ((torch.float8_e8m0fnu,) if hasattr(torch, "float8_e8m0fnu") else ())
+MX_BLOCK = 32
 
 
 def _is8(t) -> bool:
     return isinstance(t, torch.Tensor) and t.dtype in _MODE8
+
+
+def _mx_scale_f32(scales: torch.Tensor) -> torch.Tensor:
+    """E8M0 codes (uint8 or float8_e8m0fnu) as fp32: 2^(e-127) built from bits, code 0 the subnormal 2^-127, 255 NaN"""
+    if scales.dtype not in _SCALE_DTYPES:
+        raise ValueError(f"scales: dtype {scales.dtype}, expected torch.uint8 or torch.float8_e8m0fnu")
+    e = scales.view(torch.uint8).to(torch.int32)
+    bits = torch.where(e == 0, torch.full_like(e, 0x00400000), torch.where(e == 255, torch.full_like(e, 0x7FC00000), e << 23))
+    return bits.view(torch.float32)
+
+
+def mx_dequantize(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """widen(codes) * 2^(scales - 127) per block of 32 along the last dimension, one fp32 multiplication per element (the
+    dq of include/bsmr_hip.h "MX block scales"), then cast to dtype.  codes (..., K) fp8, scales (..., K/32)."""
+    if not _is8(codes):
+        raise ValueError(f"codes: dtype {getattr(codes, 'dtype', None)}, expected torch.float8_e4m3fn or torch.float8_e5m2")
+    K = codes.shape[-1]
+    if K % MX_BLOCK or tuple(scales.shape) != tuple(codes.shape[:-1]) + (K // MX_BLOCK,):
+        raise ValueError(f"scales: shape {tuple(scales.shape)} beside codes {tuple(codes.shape)}, expected one per 32 elements")
+    sc = _mx_scale_f32(scales).repeat_interleave(MX_BLOCK, dim=-1)
+    return (codes.to(torch.float32) * sc).to(dtype)
+
+
+def mx_quantize(x: torch.Tensor, fp8_dtype=torch.float8_e4m3fn):
+    """(codes, scales) of x (..., K), K a multiple of 32, in the OCP Microscaling way: per block of 32 the shared exponent
+    e = floor(log2 amax) - emax_elem + 127 clamped to [0, 254] (amax the block's largest finite magnitude; an all-zero
+    block gets 0), then x / 2^(e-127) cast with round to nearest even, saturating at the format's largest finite value
+    (+-inf saturate too, NaN stays NaN).  codes in fp8_dtype, scales torch.uint8 (..., K/32).  A finite x never dequantises
+    to a non-finite value.  A block whose amax has a mantissa above 1.75 saturates its largest e4m3 elements (the known
+    clipping of the floor rule); e5m2 mantissas end at 1.75."""
+    if fp8_dtype not in _MODE8:
+        raise ValueError(f"fp8_dtype: {fp8_dtype!r}, expected torch.float8_e4m3fn or torch.float8_e5m2")
+    K = x.shape[-1]
+    if K == 0 or K % MX_BLOCK:
+        raise ValueError(f"x: K = {K}, expected a positive multiple of 32")
+    blocks = x.to(torch.float64).reshape(tuple(x.shape[:-1]) + (K // MX_BLOCK, MX_BLOCK))
+    mag = blocks.abs()
+    amax = torch.where(torch.isfinite(mag), mag, torch.zeros_like(mag)).amax(dim=-1)
+    _, exp = torch.frexp(amax)                       # amax = f 2^exp, f in [0.5, 1): floor(log2 amax) = exp - 1
+    e = (exp.to(torch.int64) - 1 - _EMAX8[fp8_dtype] + 127).clamp(0, 254)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    scaled = blocks * torch.exp2((127 - e).to(torch.float64)).unsqueeze(-1)   # exact: a power of two in fp64
+    top = float(torch.finfo(fp8_dtype).max)
+    codes = scaled.clamp(-top, top).to(torch.float32).to(fp8_dtype).reshape(x.shape)   # clamp keeps NaN
+    return codes, e.to(torch.uint8)
 
 
 class SparseOperator:
@@ -132,20 +191,25 @@ class SparseOperator:
             self._plan = None
 
     # --- public operators ---
-    def sddmm(self, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    def sddmm(self, A: torch.Tensor, B: torch.Tensor, B_scale=None) -> torch.Tensor:
         """P = (A B^T) at S's stored positions: A (M,K) / B (N,K), or (b,M,K) / (b,N,K); P (nnz,) or (b,nnz).
-        B may be fp8 (e4m3fn / e5m2) beside an fp16 / bf16 A: no gradient reaches it."""
+        B may be fp8 (e4m3fn / e5m2) beside an fp16 / bf16 A: no gradient reaches it.  B_scale: its MX block scales."""
         if _is8(B):
             self._no_grad8(B, "B")
-            return _SDDMM8.apply(self, A, B)
+            return _SDDMM8.apply(self, A, B, None if B_scale is None else self._check_scale(B_scale, "B_scale", B))
+        self._no_scale(B_scale, "B_scale", "B")
         return _SDDMM.apply(self, A, B)
 
-    def spmm(self, values: torch.Tensor, X: torch.Tensor, transpose: bool = False, out_dtype=None) -> torch.Tensor:
+    def spmm(self, values: torch.Tensor, X: torch.Tensor, transpose: bool = False, out_dtype=None,
+             X_scale=None) -> torch.Tensor:
         """Y = S_values X (X (N,K) -> Y (M,K)) or, transposed, S_values^T X (X (M,K) -> Y (N,K)); batched with a
         leading b on values (b,nnz) and X.  fp8 X: out_dtype (torch.float16 or torch.bfloat16) is Y's dtype and
-        transpose must be False; on a blocked=True operator it takes the gather (the blocked SpMM has no fp8 form)."""
+        transpose must be False; on a blocked=True operator it takes the gather (the blocked SpMM has no fp8 form).
+        X_scale: the MX block scales of an fp8 X."""
         if self._fp8_call(X, transpose, out_dtype):
-            return _SpMM8.apply(self, values, X, out_dtype)
+            return _SpMM8.apply(self, values, X, out_dtype,
+                                None if X_scale is None else self._check_scale(X_scale, "X_scale", X))
+        self._no_scale(X_scale, "X_scale", "X")
         return _SpMM.apply(self, values, X, bool(transpose))
 
     def softmax(self, values: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
@@ -153,27 +217,33 @@ class SparseOperator:
         entries are all -inf gives zeros, a NaN or +inf makes its row NaN, rows without entries hold nothing"""
         return _Softmax.apply(self, values, scale)
 
-    def softmax_spmm(self, values: torch.Tensor, X: torch.Tensor, scale: float = 1.0, out_dtype=None) -> torch.Tensor:
+    def softmax_spmm(self, values: torch.Tensor, X: torch.Tensor, scale: float = 1.0, out_dtype=None,
+                     X_scale=None) -> torch.Tensor:
         """spmm(softmax(values, scale), X) in one gather (bsmr_sparse_attention): values (nnz,) or (b, nnz) fp32, X (N, K)
         or (b, N, K) in fp32, fp16 or bf16 -> Y (M, K) in X's dtype.  A row of S without entries, or whose entries are
-        all -inf, gives a zero row; a NaN or +inf makes its row NaN.  fp8 X: Y in out_dtype, the rule of spmm."""
+        all -inf, gives a zero row; a NaN or +inf makes its row NaN.  fp8 X: Y in out_dtype and X_scale, the rules of spmm."""
         if self._fp8_call(X, False, out_dtype):
-            return _SoftmaxSpMM8.apply(self, values, X, scale, out_dtype)
+            return _SoftmaxSpMM8.apply(self, values, X, scale, out_dtype,
+                                       None if X_scale is None else self._check_scale(X_scale, "X_scale", X))
+        self._no_scale(X_scale, "X_scale", "X")
         return _SoftmaxSpMM.apply(self, values, X, scale)
 
     def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None, fused: bool = False,
-                  out_dtype=None) -> torch.Tensor:
+                  out_dtype=None, Kt_scale=None, V_scale=None) -> torch.Tensor:
         """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
         positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row.
         fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order.
-        Kt and V may each be fp8; out_dtype (default Q.dtype) is the result's dtype when V is fp8, unused otherwise."""
-        P = self.sddmm(Q, Kt)
+        Kt and V may each be fp8; out_dtype (default Q.dtype) is the result's dtype when V is fp8, unused otherwise.
+        Kt_scale / V_scale: the MX block scales of an fp8 Kt / V, independently of each other."""
+        self._no_scale(None if _is8(Kt) else Kt_scale, "Kt_scale", "Kt")   # both refused before any device work
+        self._no_scale(None if _is8(V) else V_scale, "V_scale", "V")
+        P = self.sddmm(Q, Kt, B_scale=Kt_scale)
         if scale is None:
             scale = Q.shape[-1] ** -0.5
         out_dtype = (Q.dtype if out_dtype is None else out_dtype) if _is8(V) else None
         if fused:
-            return self.softmax_spmm(P, V, scale, out_dtype=out_dtype)
-        return self.spmm(self.softmax(P, scale), V, out_dtype=out_dtype)
+            return self.softmax_spmm(P, V, scale, out_dtype=out_dtype, X_scale=V_scale)
+        return self.spmm(self.softmax(P, scale), V, out_dtype=out_dtype, X_scale=V_scale)
 
     def stats(self) -> dict:
         return eng.backward_stats(self._bw)
@@ -186,6 +256,28 @@ class SparseOperator:
     def _no_grad8(t: torch.Tensor, name: str):
         if t.requires_grad:
             raise ValueError(f"{name}: an fp8 tensor that requires grad - no gradient is computed into fp8 operands")
+
+    @staticmethod
+    def _no_scale(scale, name: str, operand: str):
+        if scale is not None:
+            raise ValueError(f"{name}: MX block scales belong to an fp8 {operand}, this one is not fp8")
+
+    def _check_scale(self, sc, name: str, t8: torch.Tensor) -> torch.Tensor:
+        """the MX block scales of the fp8 operand t8 as a uint8 tensor; t8 itself is checked by the call"""
+        if not isinstance(sc, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch.Tensor")
+        if sc.dtype not in _SCALE_DTYPES:
+            raise ValueError(f"{name}: dtype {sc.dtype}, expected torch.float8_e8m0fnu or torch.uint8")
+        if sc.requires_grad:
+            raise ValueError(f"{name}: a scale tensor that requires grad - no gradient is computed into scales")
+        if sc.device != self.device:
+            raise ValueError(f"{name}: on {sc.device}, the operator lives on {self.device}")
+        want = tuple(t8.shape[:-1]) + (t8.shape[-1] // MX_BLOCK,) if isinstance(t8, torch.Tensor) and t8.dim() in (2, 3) else None
+        if want is None or tuple(sc.shape) != want:
+            raise ValueError(f"{name}: shape {tuple(sc.shape)}, expected {want}: the operand's batch and rows, K/32 blocks")
+        if not sc.is_contiguous():
+            raise ValueError(f"{name}: not contiguous")
+        return sc.view(torch.uint8)
 
     def _fp8_call(self, X, transpose, out_dtype) -> bool:
         """whether a call with X and out_dtype is the fp8 form; raises on the combinations neither form accepts"""
@@ -279,7 +371,7 @@ class SparseOperator:
         return Y
 
     # --- fp8 column-side operand: the 16-bit calls on the exactly widened tensor, nothing cast or copied ---
-    def _sddmm_b8(self, A: torch.Tensor, B8: torch.Tensor) -> torch.Tensor:
+    def _sddmm_b8(self, A: torch.Tensor, B8: torch.Tensor, Bs=None) -> torch.Tensor:
         b, K = self._check(A, "A", self.M, None)
         _, K2 = self._check(B8, "B", self.N, (b,), fp8=True)
         if A.dtype not in _MODE16:
@@ -287,21 +379,28 @@ class SparseOperator:
         if K2 != K:
             raise ValueError(f"A and B disagree on K ({K} vs {K2})")
         P = torch.empty((self.nnz,) if b is None else (b, self.nnz), dtype=torch.float32, device=self.device)
-        if self.nnz:
+        if self.nnz and Bs is not None:
+            eng.sddmm_b8_mx(self._plan, K, A.data_ptr(), B8.data_ptr(), Bs.data_ptr(), P.data_ptr(), b or 1, _MODE16[A.dtype],
+                            _MODE8[B8.dtype], self._stream())
+        elif self.nnz:
             eng.sddmm_b8(self._plan, K, A.data_ptr(), B8.data_ptr(), P.data_ptr(), b or 1, _MODE16[A.dtype],
                          _MODE8[B8.dtype], self._stream())
         return P
 
-    def _spmm_x8(self, v: torch.Tensor, X8: torch.Tensor, out_dtype) -> torch.Tensor:
+    def _spmm_x8(self, v: torch.Tensor, X8: torch.Tensor, out_dtype, Xs=None) -> torch.Tensor:
         """Y (M, K) in out_dtype; the gather also on a blocked operator"""
         b, K = self._check(X8, "X", self.N, None, fp8=True)
         self._check_values(v, b)
         Y = torch.empty((self.M, K) if b is None else (b, self.M, K), dtype=out_dtype, device=self.device)
+        if Xs is not None:
+            eng.spmm_x8_mx(self._bw, K, False, v.data_ptr(), X8.data_ptr(), Xs.data_ptr(), Y.data_ptr(), b or 1,
+                           self._stream(), mode=_MODE16[out_dtype], fmt=_MODE8[X8.dtype])
+            return Y
         eng.spmm_x8(self._bw, K, False, v.data_ptr(), X8.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
                     mode=_MODE16[out_dtype], fmt=_MODE8[X8.dtype])
         return Y
 
-    def _attention_x8(self, v: torch.Tensor, X8: torch.Tensor, scale, out_dtype):
+    def _attention_x8(self, v: torch.Tensor, X8: torch.Tensor, scale, out_dtype, Xs=None):
         """_attention on fp8 rows: O in out_dtype"""
         b, K = self._check(X8, "X", self.N, None, fp8=True)
         _, scale = self._softmax_args(v, scale)
@@ -309,6 +408,11 @@ class SparseOperator:
         O = torch.empty((self.M, K) if b is None else (b, self.M, K), dtype=out_dtype, device=self.device)
         m = torch.empty((self.M,) if b is None else (b, self.M), dtype=torch.float32, device=self.device)
         s = torch.empty_like(m)
+        if Xs is not None:
+            eng.sparse_attention_x8_mx(self._bw, K, scale, v.data_ptr(), X8.data_ptr(), Xs.data_ptr(), O.data_ptr(),
+                                       m.data_ptr(), s.data_ptr(), b or 1, self._stream(), mode=_MODE16[out_dtype],
+                                       fmt=_MODE8[X8.dtype])
+            return O, m, s
         eng.sparse_attention_x8(self._bw, K, scale, v.data_ptr(), X8.data_ptr(), O.data_ptr(), m.data_ptr(), s.data_ptr(),
                                 b or 1, self._stream(), mode=_MODE16[out_dtype], fmt=_MODE8[X8.dtype])
         return O, m, s
@@ -420,37 +524,37 @@ class _SDDMM(torch.autograd.Function):
 
 
 class _SDDMM8(torch.autograd.Function):
-    """sddmm with an fp8 B: dA = S_dP widen(B8) in A's dtype, nothing into B"""
+    """sddmm with an fp8 B: dA = S_dP widen(B8) in A's dtype, nothing into B; Bs: B's MX block scales, dq for widen"""
     @staticmethod
-    def forward(ctx, op: SparseOperator, A, B8):
-        ctx.op = op
+    def forward(ctx, op: SparseOperator, A, B8, Bs):
+        ctx.op, ctx.Bs = op, Bs
         ctx.save_for_backward(A, B8)
-        return op._sddmm_b8(A, B8)
+        return op._sddmm_b8(A, B8, Bs)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dP):
         A, B8 = ctx.saved_tensors
         if not ctx.needs_input_grad[1]:
-            return None, None, None
-        return None, ctx.op._spmm_x8(_grad(dP), B8, A.dtype), None
+            return None, None, None, None
+        return None, ctx.op._spmm_x8(_grad(dP), B8, A.dtype, ctx.Bs), None, None
 
 
 class _SpMM8(torch.autograd.Function):
-    """spmm with an fp8 X: d values = sddmm(dY, widen(X8)), nothing into X"""
+    """spmm with an fp8 X: d values = sddmm(dY, widen(X8)), nothing into X; Xs: X's MX block scales, dq for widen"""
     @staticmethod
-    def forward(ctx, op: SparseOperator, values, X8, out_dtype):
-        ctx.op, ctx.out_dtype = op, out_dtype
+    def forward(ctx, op: SparseOperator, values, X8, out_dtype, Xs):
+        ctx.op, ctx.out_dtype, ctx.Xs = op, out_dtype, Xs
         ctx.save_for_backward(X8)
-        return op._spmm_x8(values, X8, out_dtype)
+        return op._spmm_x8(values, X8, out_dtype, Xs)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dY):
         (X8,) = ctx.saved_tensors
         if not ctx.needs_input_grad[1]:
-            return None, None, None, None
-        return None, ctx.op._sddmm_b8(_grad(dY, ctx.out_dtype), X8), None, None
+            return None, None, None, None, None
+        return None, ctx.op._sddmm_b8(_grad(dY, ctx.out_dtype), X8, ctx.Xs), None, None, None
 
 
 class _SpMM(torch.autograd.Function):
@@ -514,11 +618,11 @@ class _SoftmaxSpMM(torch.autograd.Function):
 
 
 class _SoftmaxSpMM8(torch.autograd.Function):
-    """softmax_spmm with an fp8 X: the backward of _SoftmaxSpMM without dX"""
+    """softmax_spmm with an fp8 X: the backward of _SoftmaxSpMM without dX; Xs: X's MX block scales"""
     @staticmethod
-    def forward(ctx, op: SparseOperator, values, X8, scale, out_dtype):
-        O, m, s = op._attention_x8(values, X8, scale, out_dtype)
-        ctx.op, ctx.scale = op, float(scale)
+    def forward(ctx, op: SparseOperator, values, X8, scale, out_dtype, Xs):
+        O, m, s = op._attention_x8(values, X8, scale, out_dtype, Xs)
+        ctx.op, ctx.scale, ctx.Xs = op, float(scale), Xs
         ctx.save_for_backward(values, X8, m, s, O)
         return O
 
@@ -527,11 +631,11 @@ class _SoftmaxSpMM8(torch.autograd.Function):
     def backward(ctx, dO):
         op = ctx.op
         if not ctx.needs_input_grad[1]:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         values, X8, m, s, O = ctx.saved_tensors
         dO = _grad(dO, O.dtype)
-        dP, _ = op._attention_backward(values, m, s, op._sddmm_b8(dO, X8), O, dO, ctx.scale)
-        return None, dP, None, None, None
+        dP, _ = op._attention_backward(values, m, s, op._sddmm_b8(dO, X8, ctx.Xs), O, dO, ctx.scale)
+        return None, dP, None, None, None, None
 
 
-__all__ = ["SparseOperator"]
+__all__ = ["SparseOperator", "mx_quantize", "mx_dequantize"]

@@ -784,6 +784,45 @@ int bsmr_sparse_attention_x8(bsmr_backward *bw, uint32_t Kv, float scale, const 
                              void *O16_dev, float *m_dev, float *s_dev, uint32_t num_batches, int compute_mode,
                              int fp8_format, void *stream);
 
+/* ---- MX block scales on the fp8 operand (MXFP8; revision 5, added without any layout change; no reference counterpart) ----
+ * The fp8 operand of the four calls above with the block scales of the OCP Microscaling format, as an MXFP8 KV cache holds
+ * them: `scales` is a uint8 array [b][rows][K / 32], contiguous (batch stride rows * K / 32), one E8M0 byte per 32
+ * consecutive elements of a row.  It is read by byte loads and may have any alignment.  Code e means 2^(e - 127): e = 0 is
+ * 2^-127 (an fp32 subnormal), e = 254 is 2^127, e = 255 is NaN, as torch.float8_e8m0fnu decodes it.
+ *
+ * Numerical contract.  dq(X8, E)[r][k] = widen(X8[r][k]) * 2^(E[r][k / 32] - 127): one IEEE fp32 multiplication of the
+ * exactly widened code.  Subnormal results are kept, overflow gives +-inf, +-0 keeps its sign, e5m2's +-inf stays +-inf, a
+ * NaN code or scale code 255 gives NaN.  The element is dequantised first and then enters the fma chain; the scale is not
+ * folded into the weight (w * 2^s agrees in range but is another function at the ends of the range).  With narrow = the
+ * cast of the 16-bit forms (round to nearest even, fp16 subnormals kept, +-inf beyond the range):
+ *   bsmr_widen_fp8_mx(in8, scales, out16, count)   out16[i] = narrow(dq(in8, scales)[i]); count a multiple of 32
+ *   bsmr_sddmm_b8_mx(A16, B8, Bs)               == bsmr_sddmm_16(A16, narrow(dq(B8, Bs)))
+ *   bsmr_spmm_x8_mx(v, X8, Xs)                  == narrow(bsmr_spmm(v, dq(X8, Xs))): the fp32 gather contract of "SDDMM
+ *                                                  backward" on dq, each output rounded once; both directions
+ *   bsmr_sparse_attention_x8_mx(P, V8, Vs)      == bsmr_sparse_attention(P, dq(V8, Vs)) with O rounded once; m and s are
+ *                                                  bit for bit those of the fp32 call
+ * With every scale code 127 each call equals its unscaled call above in bits.
+ * The narrowing in bsmr_sddmm_b8_mx is exact, wherever the product is finite, with BSMR_COMPUTE_BF16 for e4m3 with scale
+ * codes >= 3 and e5m2 with scale codes >= 10; with BSMR_COMPUTE_F16 only for shifts e - 127 in [-15, 7] (e4m3) and [-8, 0]
+ * (e5m2).  Outside these ranges it rounds or overflows to +-inf: use bf16 beside an MXFP8 Kt.
+ *
+ * Each function has the argument list of its unscaled form with the scales directly after the fp8 pointer, and its
+ * checks in the same order; the scales pointer is checked with the other pointers: NULL is BSMR_ERR_INVALID_ARG unless
+ * nnz = 0 (count = 0 for bsmr_widen_fp8_mx), no alignment is demanded.  bsmr_widen_fp8_mx: a count that is not a
+ * multiple of 32 is BSMR_ERR_INVALID_ARG.  bsmr_sddmm_b8_mx dequantises into the plan's 16-bit workspace as bsmr_sddmm_b8
+ * widens; the two gathers read one scale byte per source row and lane and make no copy.  Workspaces, lists, chunks and
+ * reproducibility are those of the unscaled calls. */
+int bsmr_widen_fp8_mx(const void *in8_dev, const void *scales_dev, void *out16_dev, uint64_t count, int compute_mode,
+                      int fp8_format, void *stream);
+int bsmr_sddmm_b8_mx(bsmr_plan *plan, uint32_t K, const void *A16_dev, const void *B8_dev, const void *B_scales_dev,
+                     float *P_dev, uint32_t num_batches, int compute_mode, int fp8_format, void *stream);
+int bsmr_spmm_x8_mx(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const void *X8_dev,
+                    const void *X_scales_dev, void *Y16_dev, uint32_t num_batches, int compute_mode, int fp8_format,
+                    void *stream);
+int bsmr_sparse_attention_x8_mx(bsmr_backward *bw, uint32_t Kv, float scale, const float *P_dev, const void *V8_dev,
+                                const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev, uint32_t num_batches,
+                                int compute_mode, int fp8_format, void *stream);
+
 /* ---- Blocked SpMM: Y = S_v X over the RPHM's dense 16 x 16 blocks (revision 5, added without any layout change) ----
  * The row direction of bsmr_spmm with the dense part of the reordering put to use: in a row panel the 16 columns of a
  * dense block are shared by 16 output rows, so a row of X is read once per block instead of once per stored entry and the
