@@ -54,76 +54,69 @@ int launchAttnRowMax(const bsmr_backward* bw, float scale, const float* P, float
     return BSMR_OK;
 }
 
+// withMode with the fp32 arm of attnReduce and attnRowDot: MODE -1 for an fp32 O
+template <typename F>
+auto withModeOrF32(int mode, F&& fn) {
+    return mode == BSMR_COMPUTE_F16 ? fn(Int<0>{}) : mode == BSMR_COMPUTE_BF16 ? fn(Int<1>{}) : fn(Int<-1>{});
+}
+
 // The split rows: the pass behind the gather.  mode: BSMR_COMPUTE_F32 for an fp32 O, else its 16-bit format.
 int launchAttnReduce(const bsmr_backward* bw, uint32_t Kv, const float* partial, const float* sPart, const float* m, void* O,
                      float* sOut, uint32_t nb, int mode, hipStream_t s) {
     if (bw->numSplits[0]) {
         const uint64_t threads = (uint64_t)bw->numSplits[0] * (Kv / 4u);
         const dim3 rgrid((uint32_t)((threads + 255u) / 256u), nb);
-#define BSMR_ATTN_REDUCE(MODE)                                                                                            \
-    hipLaunchKernelGGL(bsmr::attnReduce<MODE>, rgrid, dim3(256), 0, s, bw->splits[0], bw->numSplits[0], partial, sPart,  \
-                       m, O, sOut, Kv, bw->M, bw->numSlots[0])
-        if (mode == BSMR_COMPUTE_F16) BSMR_ATTN_REDUCE(0);
-        else if (mode == BSMR_COMPUTE_BF16) BSMR_ATTN_REDUCE(1);
-        else BSMR_ATTN_REDUCE(-1);
-#undef BSMR_ATTN_REDUCE
+        withModeOrF32(mode, [&](auto MODE) {
+            hipLaunchKernelGGL(bsmr::attnReduce<MODE()>, rgrid, dim3(256), 0, s, bw->splits[0], bw->numSplits[0], partial, sPart,
+                               m, O, sOut, Kv, bw->M, bw->numSlots[0]);
+        });
         BSMR_HIP(hipGetLastError());
     }
     return BSMR_OK;
 }
 
-// mode: BSMR_COMPUTE_F32 for fp32 V / O, else the 16-bit format of both
+// t: the element types of V and O as in runGather (O has V's 16-bit format, or t.mode's with fp8 rows; y16 is not read)
 int runAttention(bsmr_backward* bw, uint32_t Kv, float scale, const float* P, const void* V, void* O, float* m, float* sOut,
-                 uint32_t nb, int mode, hipStream_t s) {
+                 uint32_t nb, hipStream_t s, const GatherTypes& t = {}) {
     if (int st = growWork(bw, attnWorkFloats(bw, Kv, nb))) return st;
     float* partial = bw->work;
     float* sPart = bw->work + attnSumsOffset(bw, Kv, nb);
     const uint32_t M = bw->M, slots = bw->numSlots[0];
     const uint64_t nnz = bw->nnz, xB = (uint64_t)bw->N * Kv;
     if (int st = launchAttnRowMax(bw, scale, P, m, nb, s)) return st;
-    const uint32_t W = Kv % 256u == 0 ? 256u : Kv % 128u == 0 ? 128u : Kv % 64u == 0 ? 64u : 32u;
-    const uint32_t slices = Kv / W;
-    const uint64_t units = (uint64_t)bw->numItems[0] * slices;
-    const bool lowp = mode != BSMR_COMPUTE_F32;
-    const uint32_t VE = lowp ? lanes16For(bw, W) : 0u;
-    const uint64_t unitsPerBlock = lowp ? 4u * (64u / (W / VE)) : 4u * (W >= 128u ? 1u : 64u / (W / 4u));
-    const dim3 grid((uint32_t)((units + unitsPerBlock - 1) / unitsPerBlock), nb);
-    if (units && lowp) {
-        const uint16_t* V16 = static_cast<const uint16_t*>(V);
+    const RowKind kind = rowKind(t);
+    const GatherGeometry g = gatherGeometry(bw, Kv, bw->numItems[0], nb, kind);
+    if (g.units) {
+        // (what every attention gather takes; `mx`: the two MX arguments of the fp8 kernels)
+        auto launch = [&](auto kernel, auto* X, auto* Out, auto... mx) {
+            hipLaunchKernelGGL(kernel, g.grid, dim3(256), 0, s, bw->items[0], bw->numItems[0], g.slices, bw->colIndices, scale, P,
+                               m, X, Out, sOut, partial, sPart, Kv, M, slots, nnz, xB, mx...);
+        };
         uint16_t* O16 = static_cast<uint16_t*>(O);
-#define BSMR_ATTN16_LAUNCH(WW, VV)                                                                                        \
-    if (mode == BSMR_COMPUTE_F16)                                                                                         \
-        hipLaunchKernelGGL((bsmr::attnGather16<WW, VV, 0>), grid, dim3(256), 0, s, bw->items[0], bw->numItems[0], slices, \
-                           bw->colIndices, scale, P, m, V16, O16, sOut, partial, sPart, Kv, M, slots, nnz, xB);           \
-    else                                                                                                                  \
-        hipLaunchKernelGGL((bsmr::attnGather16<WW, VV, 1>), grid, dim3(256), 0, s, bw->items[0], bw->numItems[0], slices, \
-                           bw->colIndices, scale, P, m, V16, O16, sOut, partial, sPart, Kv, M, slots, nnz, xB)
-#define BSMR_ATTN16_WIDTH(WW)                                                                                             \
-    if (VE == 8u) { BSMR_ATTN16_LAUNCH(WW, 8); } else { BSMR_ATTN16_LAUNCH(WW, 4); }
-        switch (W) {
-        case 256: BSMR_ATTN16_WIDTH(256); break;
-        case 128: BSMR_ATTN16_WIDTH(128); break;
-        case 64: BSMR_ATTN16_WIDTH(64); break;
-        default: BSMR_ATTN16_WIDTH(32); break;
+        if (kind == RowKind::FP8) {
+            const uint8_t* V8 = static_cast<const uint8_t*>(V);
+            withGatherShape<RowKind::FP8>(g, [&](auto W, auto LANES) {
+                withMode(t.mode, [&](auto MODE) {
+                    withFp8(t.fp8, [&](auto FMT) {
+                        if (t.scales) launch(bsmr::attnGather8<W(), LANES(), MODE(), FMT(), true>, V8, O16, t.scales, xB / 32u);
+                        else launch(bsmr::attnGather8<W(), LANES(), MODE(), FMT()>, V8, O16, kNoScales, (uint64_t)0);
+                    });
+                });
+            });
+        } else if (kind == RowKind::B16) {
+            withGatherShape<RowKind::B16>(g, [&](auto W, auto LANES) {
+                withMode(t.mode, [&](auto MODE) {
+                    launch(bsmr::attnGather16<W(), LANES(), MODE()>, static_cast<const uint16_t*>(V), O16);
+                });
+            });
+        } else {
+            withGatherShape<RowKind::F32>(g, [&](auto W, auto) {
+                launch(bsmr::attnGather<W()>, static_cast<const float*>(V), static_cast<float*>(O));
+            });
         }
-#undef BSMR_ATTN16_WIDTH
-#undef BSMR_ATTN16_LAUNCH
-        BSMR_HIP(hipGetLastError());
-    } else if (units) {
-#define BSMR_ATTN_LAUNCH(WW)                                                                                              \
-    hipLaunchKernelGGL((bsmr::attnGather<WW>), grid, dim3(256), 0, s, bw->items[0], bw->numItems[0], slices,              \
-                       bw->colIndices, scale, P, m, static_cast<const float*>(V), static_cast<float*>(O), sOut, partial, \
-                       sPart, Kv, M, slots, nnz, xB)
-        switch (W) {
-        case 256: BSMR_ATTN_LAUNCH(256); break;
-        case 128: BSMR_ATTN_LAUNCH(128); break;
-        case 64: BSMR_ATTN_LAUNCH(64); break;
-        default: BSMR_ATTN_LAUNCH(32); break;
-        }
-#undef BSMR_ATTN_LAUNCH
         BSMR_HIP(hipGetLastError());
     }
-    return launchAttnReduce(bw, Kv, partial, sPart, m, O, sOut, nb, mode, s);
+    return launchAttnReduce(bw, Kv, partial, sPart, m, O, sOut, nb, t.mode, s);
 }
 
 int runAttentionBackward(bsmr_backward* bw, uint32_t Kv, float scale, const float* P, const float* m, const float* sIn,
@@ -133,9 +126,7 @@ int runAttentionBackward(bsmr_backward* bw, uint32_t Kv, float scale, const floa
     float* D = bw->work + attnSumsOffset(bw, Kv, nb) + (uint64_t)bw->numSlots[0] * nb;
     const uint64_t rows = (uint64_t)bw->M * nb;
     const dim3 dgrid((uint32_t)((rows + 7u) / 8u));
-    if (mode == BSMR_COMPUTE_F16) hipLaunchKernelGGL(bsmr::attnRowDot<0>, dgrid, dim3(256), 0, s, O, dO, D, rows, Kv);
-    else if (mode == BSMR_COMPUTE_BF16) hipLaunchKernelGGL(bsmr::attnRowDot<1>, dgrid, dim3(256), 0, s, O, dO, D, rows, Kv);
-    else hipLaunchKernelGGL(bsmr::attnRowDot<-1>, dgrid, dim3(256), 0, s, O, dO, D, rows, Kv);
+    withModeOrF32(mode, [&](auto MODE) { hipLaunchKernelGGL(bsmr::attnRowDot<MODE()>, dgrid, dim3(256), 0, s, O, dO, D, rows, Kv); });
     BSMR_HIP(hipGetLastError());
     const uint32_t shortBlocks = attnShortBlocks(bw);
     hipLaunchKernelGGL(bsmr::attnValuesBackward, dim3(shortBlocks + bw->numSplits[0], nb), dim3(256), 0, s, bw->rowOffsets,
@@ -160,8 +151,7 @@ int bsmr_sparse_attention(bsmr_backward* bw, uint32_t Kv, float scale, const flo
     if (!aligned16(O_dev) || !aligned4(m_dev) || !aligned4(s_dev)) return BSMR_ERR_INVALID_ARG;
     if (num_batches == 0) return BSMR_OK;
     BSMR_HIP(hipSetDevice(bw->device));
-    return runAttention(bw, Kv, scale, P_dev, V_dev, O_dev, m_dev, s_dev, num_batches, BSMR_COMPUTE_F32,
-                        static_cast<hipStream_t>(stream));
+    return runAttention(bw, Kv, scale, P_dev, V_dev, O_dev, m_dev, s_dev, num_batches, static_cast<hipStream_t>(stream));
 }
 
 int bsmr_sparse_attention_16(bsmr_backward* bw, uint32_t Kv, float scale, const float* P_dev, const void* V16_dev,
@@ -171,8 +161,8 @@ int bsmr_sparse_attention_16(bsmr_backward* bw, uint32_t Kv, float scale, const 
     if (!aligned16(O16_dev) || !aligned4(m_dev) || !aligned4(s_dev)) return BSMR_ERR_INVALID_ARG;
     if (num_batches == 0) return BSMR_OK;
     BSMR_HIP(hipSetDevice(bw->device));
-    return runAttention(bw, Kv, scale, P_dev, V16_dev, O16_dev, m_dev, s_dev, num_batches, compute_mode,
-                        static_cast<hipStream_t>(stream));
+    return runAttention(bw, Kv, scale, P_dev, V16_dev, O16_dev, m_dev, s_dev, num_batches, static_cast<hipStream_t>(stream),
+                        {compute_mode, true});
 }
 
 int bsmr_sparse_attention_backward(bsmr_backward* bw, uint32_t Kv, float scale, const float* P_dev, const float* m_dev,

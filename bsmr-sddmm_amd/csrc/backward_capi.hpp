@@ -11,6 +11,7 @@
 #pragma once
 
 #include "spmm_blocked_kernels.hpp"   // (includes spmm_kernels.hpp)
+#include "fp8_kernels.hpp"            // the fp8 arms of runGather and runAttention (includes attention_kernels.hpp)
 
 // Device format of bsmr_backward_attach_blocks (csrc/blocked_capi.hpp).  Residue lists: [0] the rows outside panels with
 // blocks (destination = the row of Y), [1] the rows of panels with blocks (destination = their staging row); the chunk
@@ -131,10 +132,9 @@ int roundOperands(int mode, const float* X0, uint64_t n0, uint16_t* O0, const fl
     const uint64_t n8 = (n0 + n1) / 8u;
     if (n8 == 0) return BSMR_OK;
     const dim3 grid((uint32_t)std::min<uint64_t>((n8 + bsmr::kThreads - 1) / bsmr::kThreads, 256u * 16u));
-    if (mode == BSMR_COMPUTE_F16)
-        hipLaunchKernelGGL(bsmr::convertOperands<0>, grid, dim3(bsmr::kThreads), 0, s, X0, n0 / 8u, X1, n1 / 8u, O0, O1, false);
-    else
-        hipLaunchKernelGGL(bsmr::convertOperands<1>, grid, dim3(bsmr::kThreads), 0, s, X0, n0 / 8u, X1, n1 / 8u, O0, O1, false);
+    withMode(mode, [&](auto MODE) {
+        hipLaunchKernelGGL(bsmr::convertOperands<MODE()>, grid, dim3(bsmr::kThreads), 0, s, X0, n0 / 8u, X1, n1 / 8u, O0, O1, false);
+    });
     BSMR_HIP(hipGetLastError());
     return BSMR_OK;
 }
@@ -145,29 +145,6 @@ int roundOperands(int mode, const float* X0, uint64_t n0, uint16_t* O0, const fl
 uint32_t lanes16For(const bsmr_backward* bw, uint32_t W) {
     if (bw->lanes16) return (uint32_t)bw->lanes16;
     return W >= 128u ? 8u : 4u;
-}
-
-template <int W, int VE, typename... Args>
-void launchGather16(bool map, int mode, dim3 grid, hipStream_t s, Args... args) {
-    if (mode == BSMR_COMPUTE_F16) {
-        if (map) hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, true, 0>), grid, dim3(256), 0, s, args...);
-        else hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, false, 0>), grid, dim3(256), 0, s, args...);
-    } else {
-        if (map) hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, true, 1>), grid, dim3(256), 0, s, args...);
-        else hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, false, 1>), grid, dim3(256), 0, s, args...);
-    }
-}
-
-// ... with the finished rows stored in the format of X (bsmr_spmm_16, bsmr_sddmm_backward_16)
-template <int W, int VE, typename... Args>
-void launchGather16Out(bool map, int mode, dim3 grid, hipStream_t s, Args... args) {
-    if (mode == BSMR_COMPUTE_F16) {
-        if (map) hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, true, 0, uint16_t>), grid, dim3(256), 0, s, args...);
-        else hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, false, 0, uint16_t>), grid, dim3(256), 0, s, args...);
-    } else {
-        if (map) hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, true, 1, uint16_t>), grid, dim3(256), 0, s, args...);
-        else hipLaunchKernelGGL((bsmr::spmmGather16<W, VE, false, 1, uint16_t>), grid, dim3(256), 0, s, args...);
-    }
 }
 
 int growWork(bsmr_backward* bw, uint64_t floats) {
@@ -196,84 +173,136 @@ struct GatherLists {
     const uint32_t* map;
 };
 
-// The gather and the reduction of its split destinations over one set of lists.  xMode says what the rows of X are: fp32
-// (spmmGather), or fp16 / bf16 (spmmGather16).  y16 (16-bit X only): Yout holds xMode's format too; otherwise fp32.
-// vB / xB / yB / pB: the batch strides of v, X, Y and the partials, in elements.
+// ---- the launch of a gather (spmmGather*, attnGather*): its geometry and its compile-time shape, stated once ----------
+// What the gathered rows are: fp32, fp16 / bf16, or OCP fp8 bytes.
+enum class RowKind { F32, B16, FP8 };
+
+// Source bytes per lane of the fp8 gathers for slice width W (csrc/fp8_kernels.hpp "Lane layout")
+constexpr uint32_t lanes8For(uint32_t W) { return W >= 128u ? 16u : 8u; }
+
+constexpr const uint8_t* kNoScales = nullptr;   // the E of an fp8 gather without MX: never read
+
+// the fp8 format of a call: FMT 0 = e4m3fn, 1 = e5m2 (callers have refused every other format)
+template <typename F>
+auto withFp8(int fmt, F&& fn) {
+    return fmt == BSMR_FP8_E4M3 ? fn(Int<0>{}) : fn(Int<1>{});
+}
+
+struct GatherGeometry {
+    uint32_t W;        // slice width: the largest of 256, 128, 64, 32 that divides K
+    uint32_t slices;   // per row
+    uint32_t lanes;    // elements (fp8: bytes) a lane loads at once; 0 for fp32 rows, whose kernels have one layout per W
+    uint64_t units;    // items x slices: a unit is one slice of one item
+    dim3 grid;
+};
+
+GatherGeometry gatherGeometry(const bsmr_backward* bw, uint32_t K, uint32_t numItems, uint32_t nb, RowKind kind) {
+    GatherGeometry g;
+    g.W = K % 256u == 0 ? 256u : K % 128u == 0 ? 128u : K % 64u == 0 ? 64u : 32u;
+    g.slices = K / g.W;
+    g.units = (uint64_t)numItems * g.slices;
+    g.lanes = kind == RowKind::F32 ? 0u : kind == RowKind::B16 ? lanes16For(bw, g.W) : lanes8For(g.W);
+    // four waves per block; a unit takes W / lanes lanes of a wave - of fp32 rows W / 4, and the whole wave from W = 128 on
+    const uint64_t unitsPerBlock =
+        kind == RowKind::F32 ? 4u * (g.W >= 128u ? 1u : 64u / (g.W / 4u)) : 4u * (64u / (g.W / g.lanes));
+    g.grid = dim3((uint32_t)((g.units + unitsPerBlock - 1) / unitsPerBlock), nb);
+    return g;
+}
+
+// fn(W, LANES) with g's slice width and lane layout as compile-time constants.  KIND says which pairs exist, so a caller
+// instantiates its kernel for exactly these: fp32 rows every W (LANES = 0, not a template argument of those kernels);
+// 16-bit rows every W x {4, 8} (BSMR_GATHER16_LANES forces either); fp8 rows (256, 16), (128, 16), (64, 8), (32, 8) alone.
+template <RowKind KIND, typename F>
+void withGatherShape(const GatherGeometry& g, F&& fn) {
+    auto width = [&](auto W) {
+        if constexpr (KIND == RowKind::F32) fn(W, Int<0>{});
+        else if constexpr (KIND == RowKind::FP8) fn(W, Int<(int)lanes8For(W())>{});
+        else if (g.lanes == 8u) fn(W, Int<8>{});
+        else fn(W, Int<4>{});
+    };
+    switch (g.W) {
+    case 256: width(Int<256>{}); break;
+    case 128: width(Int<128>{}); break;
+    case 64: width(Int<64>{}); break;
+    default: width(Int<32>{}); break;
+    }
+}
+
+// The element types of a gather.  mode BSMR_COMPUTE_F32: fp32 rows of X into fp32 rows of Y.  Otherwise the rows of X
+// are mode's 16-bit format, and with y16 so are the rows of Y (else fp32).  fp8 >= 0: X holds bytes of that fp8 format
+// instead, widened to mode (y16 is then set); scales non-NULL: each multiplied by its MX block scale ([b][rows][K / 32]).
+struct GatherTypes {
+    int mode = BSMR_COMPUTE_F32;
+    bool y16 = false;
+    int fp8 = -1;
+    const uint8_t* scales = nullptr;
+};
+
+RowKind rowKind(const GatherTypes& t) {
+    return t.fp8 >= 0 ? RowKind::FP8 : t.mode != BSMR_COMPUTE_F32 ? RowKind::B16 : RowKind::F32;
+}
+
+// The gather and the reduction of its split destinations over one set of lists.  vB / xB / yB / pB: the batch strides of
+// v, X, Y and the partials, in elements.
 int runGather(const bsmr_backward* bw, const GatherLists& L, uint32_t K, const float* v, const void* Xrows, void* Yout,
-              float* partial, uint64_t vB, uint64_t xB, uint64_t yB, uint64_t pB, uint32_t nb, hipStream_t s, int xMode,
-              bool y16) {
-    const bool lowp = xMode != BSMR_COMPUTE_F32;
-    float* Y = y16 ? nullptr : static_cast<float*>(Yout);
-    uint16_t* Y16 = y16 ? static_cast<uint16_t*>(Yout) : nullptr;
-    const float* X = lowp ? nullptr : static_cast<const float*>(Xrows);
-    const uint16_t* X16 = lowp ? static_cast<const uint16_t*>(Xrows) : nullptr;
+              float* partial, uint64_t vB, uint64_t xB, uint64_t yB, uint64_t pB, uint32_t nb, hipStream_t s,
+              const GatherTypes& t = {}) {
+    const RowKind kind = rowKind(t);
+    const GatherGeometry g = gatherGeometry(bw, K, L.numItems, nb, kind);
     const uint64_t nnz = vB;
-    const uint32_t* src = L.src;
-    const uint32_t* map = L.map;
-    const uint32_t W = K % 256u == 0 ? 256u : K % 128u == 0 ? 128u : K % 64u == 0 ? 64u : 32u;
-    const uint32_t slices = K / W;
-    const uint64_t units = (uint64_t)L.numItems * slices;
-    const uint32_t VE = lowp ? lanes16For(bw, W) : 0u;
-    const uint64_t unitsPerBlock = lowp ? 4u * (64u / (W / VE)) : 4u * (W >= 128u ? 1u : 64u / (W / 4u));
-    const dim3 grid((uint32_t)((units + unitsPerBlock - 1) / unitsPerBlock), nb);
-    if (units && y16) {
-#define BSMR_SPMM16_OUT_LAUNCH(WW)                                                                                           \
-    if (VE == 8u)                                                                                                            \
-        launchGather16Out<WW, 8>(map != nullptr, xMode, grid, s, L.items, L.numItems, slices, src, map, v, X16,              \
-                                 Y16, partial, K, nnz, xB, yB, pB);                                                          \
-    else                                                                                                                     \
-        launchGather16Out<WW, 4>(map != nullptr, xMode, grid, s, L.items, L.numItems, slices, src, map, v, X16,              \
-                                 Y16, partial, K, nnz, xB, yB, pB)
-        switch (W) {
-        case 256: BSMR_SPMM16_OUT_LAUNCH(256); break;
-        case 128: BSMR_SPMM16_OUT_LAUNCH(128); break;
-        case 64: BSMR_SPMM16_OUT_LAUNCH(64); break;
-        default: BSMR_SPMM16_OUT_LAUNCH(32); break;
+    if (g.units) {
+        // (what every spmm gather takes; `scales`: the two MX arguments of the fp8 kernels)
+        auto launch = [&](auto kernel, auto* X, auto* Y, auto... scales) {
+            hipLaunchKernelGGL(kernel, g.grid, dim3(256), 0, s, L.items, L.numItems, g.slices, L.src, L.map, v, X, Y, partial, K,
+                               nnz, xB, yB, pB, scales...);
+        };
+        const bool map = L.map != nullptr;
+        if (kind == RowKind::FP8) {
+            const uint8_t* X8 = static_cast<const uint8_t*>(Xrows);
+            uint16_t* Y16 = static_cast<uint16_t*>(Yout);
+            const uint64_t eB = xB / 32u;
+            withGatherShape<RowKind::FP8>(g, [&](auto W, auto LANES) {
+                withFlag(map, [&](auto MAP) {
+                    withMode(t.mode, [&](auto MODE) {
+                        withFp8(t.fp8, [&](auto FMT) {
+                            if (t.scales) launch(bsmr::spmmGather8<W(), LANES(), MAP(), MODE(), FMT(), true>, X8, Y16, t.scales, eB);
+                            else launch(bsmr::spmmGather8<W(), LANES(), MAP(), MODE(), FMT()>, X8, Y16, kNoScales, (uint64_t)0);
+                        });
+                    });
+                });
+            });
+        } else if (kind == RowKind::B16) {
+            const uint16_t* X16 = static_cast<const uint16_t*>(Xrows);
+            withGatherShape<RowKind::B16>(g, [&](auto W, auto LANES) {
+                withFlag(map, [&](auto MAP) {
+                    withMode(t.mode, [&](auto MODE) {
+                        withFlag(t.y16, [&](auto OUT16) {
+                            using YT = std::conditional_t<OUT16(), uint16_t, float>;   // the finished rows in the format of X, or fp32
+                            launch(bsmr::spmmGather16<W(), LANES(), MAP(), MODE(), YT>, X16, static_cast<YT*>(Yout));
+                        });
+                    });
+                });
+            });
+        } else {
+            withGatherShape<RowKind::F32>(g, [&](auto W, auto) {
+                withFlag(map, [&](auto MAP) {
+                    launch(bsmr::spmmGather<W(), MAP()>, static_cast<const float*>(Xrows), static_cast<float*>(Yout));
+                });
+            });
         }
-#undef BSMR_SPMM16_OUT_LAUNCH
-        BSMR_HIP(hipGetLastError());
-    } else if (units && lowp) {
-#define BSMR_SPMM16_LAUNCH(WW)                                                                                               \
-    if (VE == 8u)                                                                                                            \
-        launchGather16<WW, 8>(map != nullptr, xMode, grid, s, L.items, L.numItems, slices, src, map, v, X16, Y,              \
-                              partial, K, nnz, xB, yB, pB);                                                                  \
-    else                                                                                                                     \
-        launchGather16<WW, 4>(map != nullptr, xMode, grid, s, L.items, L.numItems, slices, src, map, v, X16, Y,              \
-                              partial, K, nnz, xB, yB, pB)
-        switch (W) {
-        case 256: BSMR_SPMM16_LAUNCH(256); break;
-        case 128: BSMR_SPMM16_LAUNCH(128); break;
-        case 64: BSMR_SPMM16_LAUNCH(64); break;
-        default: BSMR_SPMM16_LAUNCH(32); break;
-        }
-#undef BSMR_SPMM16_LAUNCH
-        BSMR_HIP(hipGetLastError());
-    } else if (units) {
-#define BSMR_SPMM_LAUNCH(WW, MAP)                                                                                            \
-    hipLaunchKernelGGL((bsmr::spmmGather<WW, MAP>), grid, dim3(256), 0, s, L.items, L.numItems, slices, src,                 \
-                       map, v, X, Y, partial, K, nnz, xB, yB, pB)
-        const bool m = map != nullptr;
-        switch (W) {
-        case 256: if (m) BSMR_SPMM_LAUNCH(256, true); else BSMR_SPMM_LAUNCH(256, false); break;
-        case 128: if (m) BSMR_SPMM_LAUNCH(128, true); else BSMR_SPMM_LAUNCH(128, false); break;
-        case 64: if (m) BSMR_SPMM_LAUNCH(64, true); else BSMR_SPMM_LAUNCH(64, false); break;
-        default: if (m) BSMR_SPMM_LAUNCH(32, true); else BSMR_SPMM_LAUNCH(32, false); break;
-        }
-#undef BSMR_SPMM_LAUNCH
         BSMR_HIP(hipGetLastError());
     }
-    if (L.numSplits && y16) {
+    if (L.numSplits) {
         const uint64_t threads = (uint64_t)L.numSplits * (K / 4u);
         const dim3 rgrid((uint32_t)((threads + 255u) / 256u), nb);
-        if (xMode == BSMR_COMPUTE_F16)
-            hipLaunchKernelGGL(bsmr::spmmReduce16<0>, rgrid, dim3(256), 0, s, L.splits, L.numSplits, partial, Y16, K, yB, pB);
+        if (t.y16)
+            withMode(t.mode, [&](auto MODE) {
+                hipLaunchKernelGGL(bsmr::spmmReduce16<MODE()>, rgrid, dim3(256), 0, s, L.splits, L.numSplits, partial,
+                                   static_cast<uint16_t*>(Yout), K, yB, pB);
+            });
         else
-            hipLaunchKernelGGL(bsmr::spmmReduce16<1>, rgrid, dim3(256), 0, s, L.splits, L.numSplits, partial, Y16, K, yB, pB);
-        BSMR_HIP(hipGetLastError());
-    } else if (L.numSplits) {
-        const uint64_t threads = (uint64_t)L.numSplits * (K / 4u);
-        hipLaunchKernelGGL(bsmr::spmmReduce, dim3((uint32_t)((threads + 255u) / 256u), nb), dim3(256), 0, s, L.splits,
-                           L.numSplits, partial, Y, K, yB, pB);
+            hipLaunchKernelGGL(bsmr::spmmReduce, rgrid, dim3(256), 0, s, L.splits, L.numSplits, partial,
+                               static_cast<float*>(Yout), K, yB, pB);
         BSMR_HIP(hipGetLastError());
     }
     return BSMR_OK;
@@ -295,15 +324,63 @@ int spmmLists(bsmr_backward* bw, uint32_t K, int dir, const float*& v, uint32_t 
     return BSMR_OK;
 }
 
-// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.  xMode / y16 as
-// runGather.
+// Y = S_v X (dir 0) or S_v^T X (dir 1) for num_batches batches; the workspace is already large enough.
 int runSpmm(bsmr_backward* bw, uint32_t K, int dir, const float* v, const void* Xrows, void* Yout, uint32_t nb, hipStream_t s,
-            int xMode = BSMR_COMPUTE_F32, bool y16 = false) {
+            const GatherTypes& t = {}) {
     const uint32_t rowsX = dir ? bw->M : bw->N, rowsY = dir ? bw->N : bw->M;
     const uint64_t xB = (uint64_t)rowsX * K, yB = (uint64_t)rowsY * K, pB = (uint64_t)bw->numSlots[dir] * K;
     GatherLists L;
     if (int st = spmmLists(bw, K, dir, v, nb, s, L)) return st;
-    return runGather(bw, L, K, v, Xrows, Yout, bw->work, bw->nnz, xB, yB, pB, nb, s, xMode, y16);
+    return runGather(bw, L, K, v, Xrows, Yout, bw->work, bw->nnz, xB, yB, pB, nb, s, t);
+}
+
+bool is16(int mode) { return mode == BSMR_COMPUTE_F16 || mode == BSMR_COMPUTE_BF16; }
+
+// The checks of every bsmr_spmm* entry point, in the order their statuses promise: the handle, K (UNSUPPORTED_K), the
+// batches, then what the entry point itself accepts as compute mode and fp8 format (modeOk), transpose, the pointers.
+// nnz = 0 reads neither v nor X nor the scales (torch hands out NULL for a zero-element tensor); Y is still written with
+// zeros.  mx: the call carries MX block scales (any alignment: byte loads).
+int checkSpmmCall(const bsmr_backward* bw, uint32_t K, bool modeOk, int transpose, uint32_t nb, const void* v, const void* X,
+                  const void* Y, const void* scales = nullptr, bool mx = false) {
+    if (int st = checkBackwardCall(bw, K, nb)) return st;
+    if (!modeOk || (transpose != 0 && transpose != 1)) return BSMR_ERR_INVALID_ARG;
+    const bool reads = bw->nnz != 0;
+    if ((reads && (!v || !X || (mx && !scales))) || !Y || !aligned4(v) || !aligned16(X) || !aligned16(Y))
+        return BSMR_ERR_INVALID_ARG;
+    return BSMR_OK;
+}
+
+// ... and of the three bsmr_sddmm_backward* ones: an output that is NULL is not computed and its operand not looked at
+int checkSddmmBackwardCall(const bsmr_backward* bw, uint32_t K, bool modeOk, uint32_t nb, const void* dP, const void* A,
+                           const void* B, const void* dA, const void* dB) {
+    if (int st = checkBackwardCall(bw, K, nb)) return st;
+    if (!modeOk) return BSMR_ERR_INVALID_ARG;
+    const bool reads = bw->nnz != 0;   // as bsmr_spmm: nnz = 0 reads no operand, the outputs are still zeroed
+    if ((reads && !dP) || !aligned4(dP) || (dA && ((reads && !B) || !aligned16(B) || !aligned16(dA))) ||
+        (dB && ((reads && !A) || !aligned16(A) || !aligned16(dB))))
+        return BSMR_ERR_INVALID_ARG;
+    return BSMR_OK;
+}
+
+// The body of the bsmr_spmm* entry points that gather the caller's rows as they are (checked, num_batches >= 1)
+int spmmCall(bsmr_backward* bw, uint32_t K, int transpose, const float* v, const void* X, void* Y, uint32_t nb, void* stream,
+             const GatherTypes& t = {}) {
+    BSMR_HIP(hipSetDevice(bw->device));
+    if (int st = growWork(bw, workFloatsFor(bw, K, nb, bw->permuteV && transpose))) return st;
+    return runSpmm(bw, K, transpose, v, X, Y, nb, static_cast<hipStream_t>(stream), t);
+}
+
+// ... and of bsmr_sddmm_backward and _16: dA = S_dP B, dB = S_dP^T A, each only where asked for
+int sddmmBackwardCall(bsmr_backward* bw, uint32_t K, const float* dP, const void* A, const void* B, void* dA, void* dB,
+                      uint32_t nb, void* stream, const GatherTypes& t = {}) {
+    BSMR_HIP(hipSetDevice(bw->device));
+    if (int st = growWork(bw, workFloatsFor(bw, K, nb, bw->permuteV && dB))) return st;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dA)
+        if (int st = runSpmm(bw, K, 0, dP, B, dA, nb, s, t)) return st;
+    if (dB)
+        if (int st = runSpmm(bw, K, 1, dP, A, dB, nb, s, t)) return st;
+    return BSMR_OK;
 }
 
 }  // namespace
@@ -411,34 +488,16 @@ int bsmr_backward_get_stats(const bsmr_backward* bw, bsmr_backward_stats* out, s
 
 int bsmr_spmm(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, const float* X_dev, float* Y_dev,
               uint32_t num_batches, void* stream) {
-    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
-    // nnz = 0 reads neither v nor X (torch hands out NULL for a zero-element tensor); Y is still written with zeros
-    const bool reads = bw->nnz != 0;
-    if ((reads && (!v_dev || !X_dev)) || !Y_dev || !aligned4(v_dev) || !aligned16(X_dev) || !aligned16(Y_dev))
-        return BSMR_ERR_INVALID_ARG;
+    if (int st = checkSpmmCall(bw, K, true, transpose, num_batches, v_dev, X_dev, Y_dev)) return st;
     if (num_batches == 0) return BSMR_OK;
-    BSMR_HIP(hipSetDevice(bw->device));
-    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
-    return runSpmm(bw, K, transpose, v_dev, X_dev, Y_dev, num_batches, static_cast<hipStream_t>(stream));
+    return spmmCall(bw, K, transpose, v_dev, X_dev, Y_dev, num_batches, stream);
 }
 
 int bsmr_sddmm_backward(bsmr_backward* bw, uint32_t K, const float* dP_dev, const float* A_dev, const float* B_dev,
                         float* dA_dev, float* dB_dev, uint32_t num_batches, void* stream) {
-    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    const bool reads = bw->nnz != 0;   // as bsmr_spmm: nnz = 0 reads no operand, the outputs are still zeroed
-    if ((reads && !dP_dev) || !aligned4(dP_dev) || (dA_dev && ((reads && !B_dev) || !aligned16(B_dev) || !aligned16(dA_dev))) ||
-        (dB_dev && ((reads && !A_dev) || !aligned16(A_dev) || !aligned16(dB_dev))))
-        return BSMR_ERR_INVALID_ARG;
+    if (int st = checkSddmmBackwardCall(bw, K, true, num_batches, dP_dev, A_dev, B_dev, dA_dev, dB_dev)) return st;
     if (num_batches == 0 || (!dA_dev && !dB_dev)) return BSMR_OK;
-    BSMR_HIP(hipSetDevice(bw->device));
-    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && dB_dev))) return st;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dA_dev)
-        if (int st = runSpmm(bw, K, 0, dP_dev, B_dev, dA_dev, num_batches, s)) return st;
-    if (dB_dev)
-        if (int st = runSpmm(bw, K, 1, dP_dev, A_dev, dB_dev, num_batches, s)) return st;
-    return BSMR_OK;
+    return sddmmBackwardCall(bw, K, dP_dev, A_dev, B_dev, dA_dev, dB_dev, num_batches, stream);
 }
 
 int bsmr_backward_reserve_mode(bsmr_backward* bw, uint32_t K, uint32_t num_batches, int compute_mode) {
@@ -453,85 +512,51 @@ int bsmr_backward_reserve_mode(bsmr_backward* bw, uint32_t K, uint32_t num_batch
 
 int bsmr_spmm_mode(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, const float* X_dev, float* Y_dev,
                    uint32_t num_batches, int compute_mode, void* stream) {
-    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    if (!validMode(compute_mode)) return BSMR_ERR_INVALID_ARG;
-    if (compute_mode == BSMR_COMPUTE_F32) return bsmr_spmm(bw, K, transpose, v_dev, X_dev, Y_dev, num_batches, stream);
-    if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
-    const bool reads = bw->nnz != 0;
-    if ((reads && (!v_dev || !X_dev)) || !Y_dev || !aligned4(v_dev) || !aligned16(X_dev) || !aligned16(Y_dev))
-        return BSMR_ERR_INVALID_ARG;
+    if (int st = checkSpmmCall(bw, K, validMode(compute_mode), transpose, num_batches, v_dev, X_dev, Y_dev)) return st;
     if (num_batches == 0) return BSMR_OK;
+    if (compute_mode == BSMR_COMPUTE_F32) return spmmCall(bw, K, transpose, v_dev, X_dev, Y_dev, num_batches, stream);
     BSMR_HIP(hipSetDevice(bw->device));
-    const uint64_t n = reads ? (uint64_t)(transpose ? bw->M : bw->N) * K * num_batches : 0u;   // nnz = 0 reads no X
+    const uint64_t n = bw->nnz ? (uint64_t)(transpose ? bw->M : bw->N) * K * num_batches : 0u;   // nnz = 0 reads no X
     const uint64_t off = lowpOffset(bw, K, num_batches, bw->permuteV && transpose);
     if (int st = growWork(bw, off + n / 2u)) return st;
     const hipStream_t s = static_cast<hipStream_t>(stream);
     uint16_t* X16 = reinterpret_cast<uint16_t*>(bw->work + off);
     if (int st = roundOperands(compute_mode, X_dev, n, X16, nullptr, 0, nullptr, s)) return st;
-    return runSpmm(bw, K, transpose, v_dev, X16, Y_dev, num_batches, s, compute_mode);
+    return runSpmm(bw, K, transpose, v_dev, X16, Y_dev, num_batches, s, {compute_mode});
 }
 
 int bsmr_spmm_lowp(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, const void* X16_dev, float* Y_dev,
                    uint32_t num_batches, int compute_mode, void* stream) {
-    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    if (compute_mode != BSMR_COMPUTE_F16 && compute_mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
-    if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
-    const bool reads = bw->nnz != 0;
-    if ((reads && (!v_dev || !X16_dev)) || !Y_dev || !aligned4(v_dev) || !aligned16(X16_dev) || !aligned16(Y_dev))
-        return BSMR_ERR_INVALID_ARG;
+    if (int st = checkSpmmCall(bw, K, is16(compute_mode), transpose, num_batches, v_dev, X16_dev, Y_dev)) return st;
     if (num_batches == 0) return BSMR_OK;
-    BSMR_HIP(hipSetDevice(bw->device));
-    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
-    return runSpmm(bw, K, transpose, v_dev, X16_dev, Y_dev, num_batches, static_cast<hipStream_t>(stream), compute_mode);
+    return spmmCall(bw, K, transpose, v_dev, X16_dev, Y_dev, num_batches, stream, {compute_mode});
 }
 
 int bsmr_spmm_16(bsmr_backward* bw, uint32_t K, int transpose, const float* v_dev, const void* X16_dev, void* Y16_dev,
                  uint32_t num_batches, int compute_mode, void* stream) {
-    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    if (compute_mode != BSMR_COMPUTE_F16 && compute_mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
-    if (transpose != 0 && transpose != 1) return BSMR_ERR_INVALID_ARG;
-    const bool reads = bw->nnz != 0;
-    if ((reads && (!v_dev || !X16_dev)) || !Y16_dev || !aligned4(v_dev) || !aligned16(X16_dev) || !aligned16(Y16_dev))
-        return BSMR_ERR_INVALID_ARG;
+    if (int st = checkSpmmCall(bw, K, is16(compute_mode), transpose, num_batches, v_dev, X16_dev, Y16_dev)) return st;
     if (num_batches == 0) return BSMR_OK;
-    BSMR_HIP(hipSetDevice(bw->device));
-    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && transpose))) return st;
-    return runSpmm(bw, K, transpose, v_dev, X16_dev, Y16_dev, num_batches, static_cast<hipStream_t>(stream), compute_mode, true);
+    return spmmCall(bw, K, transpose, v_dev, X16_dev, Y16_dev, num_batches, stream, {compute_mode, true});
 }
 
 int bsmr_sddmm_backward_16(bsmr_backward* bw, uint32_t K, const float* dP_dev, const void* A16_dev, const void* B16_dev,
                            void* dA16_dev, void* dB16_dev, uint32_t num_batches, int compute_mode, void* stream) {
-    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    if (compute_mode != BSMR_COMPUTE_F16 && compute_mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
-    const bool reads = bw->nnz != 0;
-    if ((reads && !dP_dev) || !aligned4(dP_dev) ||
-        (dA16_dev && ((reads && !B16_dev) || !aligned16(B16_dev) || !aligned16(dA16_dev))) ||
-        (dB16_dev && ((reads && !A16_dev) || !aligned16(A16_dev) || !aligned16(dB16_dev))))
-        return BSMR_ERR_INVALID_ARG;
+    if (int st = checkSddmmBackwardCall(bw, K, is16(compute_mode), num_batches, dP_dev, A16_dev, B16_dev, dA16_dev, dB16_dev))
+        return st;
     if (num_batches == 0 || (!dA16_dev && !dB16_dev)) return BSMR_OK;
-    BSMR_HIP(hipSetDevice(bw->device));
-    if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, bw->permuteV && dB16_dev))) return st;
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dA16_dev)
-        if (int st = runSpmm(bw, K, 0, dP_dev, B16_dev, dA16_dev, num_batches, s, compute_mode, true)) return st;
-    if (dB16_dev)
-        if (int st = runSpmm(bw, K, 1, dP_dev, A16_dev, dB16_dev, num_batches, s, compute_mode, true)) return st;
-    return BSMR_OK;
+    return sddmmBackwardCall(bw, K, dP_dev, A16_dev, B16_dev, dA16_dev, dB16_dev, num_batches, stream, {compute_mode, true});
 }
 
 int bsmr_sddmm_backward_mode(bsmr_backward* bw, uint32_t K, const float* dP_dev, const float* A_dev, const float* B_dev,
                              float* dA_dev, float* dB_dev, uint32_t num_batches, int compute_mode, void* stream) {
-    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    if (!validMode(compute_mode)) return BSMR_ERR_INVALID_ARG;
-    if (compute_mode == BSMR_COMPUTE_F32)
-        return bsmr_sddmm_backward(bw, K, dP_dev, A_dev, B_dev, dA_dev, dB_dev, num_batches, stream);
-    const bool reads = bw->nnz != 0;
-    if ((reads && !dP_dev) || !aligned4(dP_dev) || (dA_dev && ((reads && !B_dev) || !aligned16(B_dev) || !aligned16(dA_dev))) ||
-        (dB_dev && ((reads && !A_dev) || !aligned16(A_dev) || !aligned16(dB_dev))))
-        return BSMR_ERR_INVALID_ARG;
+    if (int st = checkSddmmBackwardCall(bw, K, validMode(compute_mode), num_batches, dP_dev, A_dev, B_dev, dA_dev, dB_dev))
+        return st;
     if (num_batches == 0 || (!dA_dev && !dB_dev)) return BSMR_OK;
+    if (compute_mode == BSMR_COMPUTE_F32)
+        return sddmmBackwardCall(bw, K, dP_dev, A_dev, B_dev, dA_dev, dB_dev, num_batches, stream);
     BSMR_HIP(hipSetDevice(bw->device));
     // B is gathered by dA, A by dB: only what a requested product reads is rounded, B16 first, A16 behind it
+    const bool reads = bw->nnz != 0;
     const uint64_t nB = reads && dA_dev ? (uint64_t)bw->N * K * num_batches : 0u;
     const uint64_t nA = reads && dB_dev ? (uint64_t)bw->M * K * num_batches : 0u;
     const uint64_t off = lowpOffset(bw, K, num_batches, bw->permuteV && dB_dev);
@@ -541,9 +566,9 @@ int bsmr_sddmm_backward_mode(bsmr_backward* bw, uint32_t K, const float* dP_dev,
     uint16_t* A16 = B16 + nB;
     if (int st = roundOperands(compute_mode, A_dev, nA, A16, B_dev, nB, B16, s)) return st;
     if (dA_dev)
-        if (int st = runSpmm(bw, K, 0, dP_dev, B16, dA_dev, num_batches, s, compute_mode)) return st;
+        if (int st = runSpmm(bw, K, 0, dP_dev, B16, dA_dev, num_batches, s, {compute_mode})) return st;
     if (dB_dev)
-        if (int st = runSpmm(bw, K, 1, dP_dev, A16, dB_dev, num_batches, s, compute_mode)) return st;
+        if (int st = runSpmm(bw, K, 1, dP_dev, A16, dB_dev, num_batches, s, {compute_mode})) return st;
     return BSMR_OK;
 }
 

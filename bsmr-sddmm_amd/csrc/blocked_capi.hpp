@@ -114,8 +114,10 @@ int blockedCheck(uint32_t M, uint32_t N, uint32_t nnz, const uint32_t* ro, const
     return BSMR_OK;
 }
 
-int checkBlockedCall(const bsmr_backward* bw, uint32_t K, uint32_t nb, const void* v, const void* X, const void* Y) {
+// modeOk: what the entry point accepts as compute mode, tested where bsmr_spmm_16 tests it (checkSpmmCall)
+int checkBlockedCall(const bsmr_backward* bw, uint32_t K, bool modeOk, uint32_t nb, const void* v, const void* X, const void* Y) {
     if (int st = checkBackwardCall(bw, K, nb)) return st;
+    if (!modeOk) return BSMR_ERR_INVALID_ARG;
     if (!bw->blocked) return BSMR_ERR_BAD_PLAN;
     const bool reads = bw->nnz != 0;   // as bsmr_spmm: nnz = 0 reads neither v nor X, Y is still zeroed
     if ((reads && (!v || !X)) || !Y || !aligned4(v) || !aligned16(X) || !aligned16(Y)) return BSMR_ERR_INVALID_ARG;
@@ -126,6 +128,8 @@ int checkBlockedCall(const bsmr_backward* bw, uint32_t K, uint32_t nb, const voi
 int runBlocked(bsmr_backward* bw, uint32_t K, const float* v, const void* X, void* Y, uint32_t nb, int mode, hipStream_t s) {
     const BwBlocked& f = *bw->blocked;
     const bool y16 = mode != BSMR_COMPUTE_F32;
+    const uint16_t* X16 = static_cast<const uint16_t*>(X);
+    uint16_t* Y16 = static_cast<uint16_t*>(Y);
     const uint64_t nnz = bw->nnz;
     const uint64_t xB = (uint64_t)bw->N * K, yB = (uint64_t)bw->M * K, pB = (uint64_t)f.numSlots * K;
     const uint64_t rB = 16ull * f.numPanels * K, sB = 16ull * f.numPartials * K;
@@ -135,8 +139,8 @@ int runBlocked(bsmr_backward* bw, uint32_t K, const float* v, const void* X, voi
     // R of the rows outside panels with blocks is their row of Y; R of the others waits in fp32 for the block chain
     const GatherLists toY{f.items[0], f.numItems[0], f.splits[0], f.numSplits[0], f.resCols, f.resIdx};
     const GatherLists toStage{f.items[1], f.numItems[1], f.splits[1], f.numSplits[1], f.resCols, f.resIdx};
-    if (int st = runGather(bw, toY, K, v, X, Y, partial, nnz, xB, yB, pB, nb, s, mode, y16)) return st;
-    if (int st = runGather(bw, toStage, K, v, X, stage, partial, nnz, xB, rB, pB, nb, s, mode, false)) return st;
+    if (int st = runGather(bw, toY, K, v, X, Y, partial, nnz, xB, yB, pB, nb, s, {mode, y16})) return st;
+    if (int st = runGather(bw, toStage, K, v, X, stage, partial, nnz, xB, rB, pB, nb, s, {mode, false})) return st;
     if (!f.numPanels) return BSMR_OK;
     const uint32_t groups = (K + 63u) / 64u;
     if (!f.segmentBlocks) {   // the panel form
@@ -146,9 +150,8 @@ int runBlocked(bsmr_backward* bw, uint32_t K, const float* v, const void* X, voi
             hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, f.panels, f.numPanels, groups, f.panelRows, f.cells, f.cols,
                                f.zeros, v, x, stage, y, bw->N, K, nnz, xB, yB, rB);
         };
-        if (mode == BSMR_COMPUTE_F32) launch(bsmr::spmmBlocks, static_cast<const float*>(X), static_cast<float*>(Y));
-        else if (mode == BSMR_COMPUTE_F16) launch(bsmr::spmmBlocks16<0>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
-        else launch(bsmr::spmmBlocks16<1>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
+        if (!y16) launch(bsmr::spmmBlocks, static_cast<const float*>(X), static_cast<float*>(Y));
+        else withMode(mode, [&](auto MODE) { launch(bsmr::spmmBlocks16<MODE()>, X16, Y16); });
         BSMR_HIP(hipGetLastError());
         return BSMR_OK;
     }
@@ -163,12 +166,8 @@ int runBlocked(bsmr_backward* bw, uint32_t K, const float* v, const void* X, voi
             hipLaunchKernelGGL(finish, finGrid, dim3(256), 0, s, f.splitPanels, f.numSplitPanels, f.panelRows, segPartial,
                                stage, y, K, sB, rB, yB);
     };
-    if (mode == BSMR_COMPUTE_F32)
-        launch(bsmr::spmmBlocksSeg, bsmr::spmmBlocksFinish, static_cast<const float*>(X), static_cast<float*>(Y));
-    else if (mode == BSMR_COMPUTE_F16)
-        launch(bsmr::spmmBlocksSeg16<0>, bsmr::spmmBlocksFinish16<0>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
-    else
-        launch(bsmr::spmmBlocksSeg16<1>, bsmr::spmmBlocksFinish16<1>, static_cast<const uint16_t*>(X), static_cast<uint16_t*>(Y));
+    if (!y16) launch(bsmr::spmmBlocksSeg, bsmr::spmmBlocksFinish, static_cast<const float*>(X), static_cast<float*>(Y));
+    else withMode(mode, [&](auto MODE) { launch(bsmr::spmmBlocksSeg16<MODE()>, bsmr::spmmBlocksFinish16<MODE()>, X16, Y16); });
     BSMR_HIP(hipGetLastError());
     return BSMR_OK;
 }
@@ -325,7 +324,7 @@ int bsmr_backward_get_blocked_stats(const bsmr_backward* bw, bsmr_blocked_stats*
 
 int bsmr_spmm_blocked(bsmr_backward* bw, uint32_t K, const float* v_dev, const float* X_dev, float* Y_dev,
                       uint32_t num_batches, void* stream) {
-    if (int st = checkBlockedCall(bw, K, num_batches, v_dev, X_dev, Y_dev)) return st;
+    if (int st = checkBlockedCall(bw, K, true, num_batches, v_dev, X_dev, Y_dev)) return st;
     if (num_batches == 0) return BSMR_OK;
     BSMR_HIP(hipSetDevice(bw->device));
     if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, false))) return st;
@@ -334,9 +333,7 @@ int bsmr_spmm_blocked(bsmr_backward* bw, uint32_t K, const float* v_dev, const f
 
 int bsmr_spmm_blocked_16(bsmr_backward* bw, uint32_t K, const float* v_dev, const void* X16_dev, void* Y16_dev,
                          uint32_t num_batches, int compute_mode, void* stream) {
-    if (int st = checkBackwardCall(bw, K, num_batches)) return st;
-    if (compute_mode != BSMR_COMPUTE_F16 && compute_mode != BSMR_COMPUTE_BF16) return BSMR_ERR_INVALID_ARG;
-    if (int st = checkBlockedCall(bw, K, num_batches, v_dev, X16_dev, Y16_dev)) return st;
+    if (int st = checkBlockedCall(bw, K, is16(compute_mode), num_batches, v_dev, X16_dev, Y16_dev)) return st;
     if (num_batches == 0) return BSMR_OK;
     BSMR_HIP(hipSetDevice(bw->device));
     if (int st = growWork(bw, workFloatsFor(bw, K, num_batches, false))) return st;

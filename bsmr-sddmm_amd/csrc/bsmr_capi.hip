@@ -14,12 +14,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <new>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "dev_array.hpp"
@@ -272,6 +274,57 @@ int upload(DevArray<T>& dst, const std::vector<T>& src, uint64_t& bytes) {
     const bool copied = dst.get() != nullptr;   // (the allocation succeeded, the copy failed)
     hipOk(e, copied ? "hipMemcpy(plan)" : "hipMalloc(plan)");
     return copied ? BSMR_ERR_HIP : BSMR_ERR_OOM;
+}
+
+// Run-time choices as the compile-time constants of the kernel templates.  Each helper calls fn once, with an
+// std::integral_constant, so a launcher names its kernel template once: withMode(mode, [&](auto MODE) { ... f<MODE()> ... }).
+// They offer exactly the arms the spelled-out pairs had: a call site that nests them instantiates its kernel for the
+// product of the arms it nests and nothing else, so a kernel built for a subset keeps its own guard ("The launch layer").
+template <int N>
+using Int = std::integral_constant<int, N>;
+// the 16-bit format of a call: MODE 0 = fp16, 1 = bf16 (callers have refused every other mode, or branched on F32 before)
+template <typename F>
+auto withMode(int mode, F&& fn) {
+    return mode == BSMR_COMPUTE_F16 ? fn(Int<0>{}) : fn(Int<1>{});
+}
+template <typename F>
+auto withFlag(bool on, F&& fn) {
+    return on ? fn(std::true_type{}) : fn(std::false_type{});
+}
+
+// A pair of timing events, destroyed with its scope.
+struct EventPair {
+    hipEvent_t start = nullptr, stop = nullptr;
+    EventPair() = default;
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+    ~EventPair() {
+        if (start) (void)hipEventDestroy(start);
+        if (stop) (void)hipEventDestroy(stop);
+    }
+    int create() {
+        BSMR_HIP(hipEventCreate(&start));
+        BSMR_HIP(hipEventCreate(&stop));
+        return BSMR_OK;
+    }
+};
+
+// `launch()` n times on s between the two events, then waits for the second: *us = microseconds per launch.  The loop
+// stops at the first launch that fails; the events are still recorded and waited for, so nothing of the loop is left
+// running.  Returns BSMR_ERR_HIP when the timing itself failed, else the status of the last launch; *us is written only
+// when both are fine.  Warm-up, repetitions and what a failure means stay with the caller.
+template <typename F>
+int timedLoop(const EventPair& ev, hipStream_t s, int n, F&& launch, float* us) {
+    hipError_t e = hipEventRecord(ev.start, s);
+    int rc = BSMR_OK;
+    for (int i = 0; i < n && rc == BSMR_OK; ++i) rc = launch();
+    if (e == hipSuccess) e = hipEventRecord(ev.stop, s);
+    if (e == hipSuccess) e = hipEventSynchronize(ev.stop);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev.start, ev.stop);
+    if (!hipOk(e, "event timing")) return BSMR_ERR_HIP;
+    if (rc == BSMR_OK) *us = ms * 1000.f / (float)n;
+    return rc;
 }
 
 // BSMR_PLAN_TIMING=1: the stages of a plan's construction on stderr, milliseconds each (the device is synchronised at every
@@ -890,22 +943,31 @@ int launchStreamT(const DenseFormat& f, const uint16_t* A16, const uint16_t* B16
     return BSMR_OK;
 }
 
+// fn(tiles) with the destination tiles of f as the array that holds them: the mask form, bytes, or the DIRECT formats'
+// 16- / 32-bit offsets.  A kernel built for some of the four (launchStreamCvtT, the LDS stage below) does not come
+// through here, or guards its arm with `if constexpr` on the pointer's type.
+template <typename F>
+int withTiles(const DenseFormat& f, F&& fn) {
+    if (f.tilesM) return fn(f.tilesM.get());
+    if (f.tiles8) return fn(f.tiles8.get());
+    return f.tiles16 ? fn(f.tiles16.get()) : fn(f.tiles32.get());
+}
+template <typename TilePtr>
+using TileOf = std::remove_const_t<std::remove_pointer_t<TilePtr>>;
+
 template <int KS, int MODE>
 int launchStream(const DenseFormat& f, const uint16_t* A16, const uint16_t* B16, float* P, const Queue& s) {
-    if (f.tilesM) return launchStreamT<KS, MODE, bsmr::TileMask>(f, A16, B16, f.tilesM, P, s);
-    if (f.tiles8) return launchStreamT<KS, MODE, uint8_t>(f, A16, B16, f.tiles8, P, s);
-    return f.tiles16 ? launchStreamT<KS, MODE, uint16_t>(f, A16, B16, f.tiles16, P, s)
-                     : launchStreamT<KS, MODE, uint32_t>(f, A16, B16, f.tiles32, P, s);
+    return withTiles(f, [&](auto* tiles) { return launchStreamT<KS, MODE, TileOf<decltype(tiles)>>(f, A16, B16, tiles, P, s); });
 }
 
 template <int KS, int H, int NB, int MODE>
 int launchGroups(const DenseFormat& f, const uint16_t* A16, const uint16_t* B16, float* P, const Queue& s) {
-    if (f.tilesM) return launchGroupsT<KS, H, NB, MODE, bsmr::TileMask, false>(f, A16, B16, f.tilesM, P, s);
-    if (f.tiles8)
-        return f.stageInLds ? launchGroupsT<KS, H, NB, MODE, uint8_t, true>(f, A16, B16, f.tiles8, P, s)
-                            : launchGroupsT<KS, H, NB, MODE, uint8_t, false>(f, A16, B16, f.tiles8, P, s);
-    return f.tiles16 ? launchGroupsT<KS, H, NB, MODE, uint16_t>(f, A16, B16, f.tiles16, P, s)
-                     : launchGroupsT<KS, H, NB, MODE, uint32_t>(f, A16, B16, f.tiles32, P, s);
+    return withTiles(f, [&](auto* tiles) {
+        using TileT = TileOf<decltype(tiles)>;
+        if constexpr (std::is_same_v<TileT, uint8_t>)   // the LDS stage exists for byte tiles alone
+            if (f.stageInLds) return launchGroupsT<KS, H, NB, MODE, uint8_t, true>(f, A16, B16, tiles, P, s);
+        return launchGroupsT<KS, H, NB, MODE, TileT, false>(f, A16, B16, tiles, P, s);
+    });
 }
 
 template <int KS, int NB, int MODE>
@@ -1008,46 +1070,70 @@ int ensureTiles(bsmr_plan* p, uint32_t H) {
     }
 }
 
+#ifdef BSMR_LAB_STAMPS
+// Lab build (make LAB=1, BSMR_TILE_STAMPS=1): one launch of a dense kernel that writes a record of eight 64-bit stamps per
+// wave.  launch(stamps) runs it on a zeroed device array of `records` records, which comes back in h.
+template <typename L>
+int collectStamps(size_t records, hipStream_t s, L&& launch, std::vector<uint64_t>& h) {
+    DevArray<uint64_t> dev;
+    const size_t n = records * 8;
+    if (!allocOk(dev, n, "hipMalloc(stamps)")) return BSMR_ERR_HIP;
+    BSMR_HIP(hipMemset(dev, 0, n * 8));
+    launch(dev.get());
+    BSMR_HIP(hipStreamSynchronize(s));
+    h.resize(n);
+    BSMR_HIP(hipMemcpy(h.data(), dev, n * 8, hipMemcpyDeviceToHost));
+    return BSMR_OK;
+}
+
+// A row of the report: stamp `hi` of a record minus stamp `lo`, minus the earliest start of the launch (kStampFirst), or
+// as it is (kStampSum: the kernel summed a phase over its loop).
+constexpr int kStampFirst = -1, kStampSum = -2;
+struct StampRow {
+    const char* name;
+    int hi, lo;
+};
+uint64_t firstStamp(const std::vector<uint64_t>& h) {
+    uint64_t first = ~0ull;
+    for (size_t i = 0; i < h.size(); i += 8) first = std::min(first, h[i]);
+    return first;
+}
+// median and 90th percentile of every row over the records, on stderr; labels padded to `width`
+void printStamps(const std::vector<uint64_t>& h, std::initializer_list<StampRow> rows, int width) {
+    const uint64_t first = firstStamp(h);
+    std::vector<double> v(h.size() / 8);
+    for (const StampRow& r : rows) {
+        for (size_t i = 0; i < v.size(); ++i) {
+            const uint64_t* q = &h[i * 8];
+            v[i] = (double)(q[r.hi] - (r.lo == kStampSum ? 0 : r.lo == kStampFirst ? first : q[r.lo]));
+        }
+        std::sort(v.begin(), v.end());
+        fprintf(stderr, "  %-*s median %9.0f  p90 %9.0f\n", width, r.name, v[v.size() / 2], v[v.size() * 9 / 10]);
+    }
+}
+#endif
+
 template <int KS, int H, int MODE, int DEPTH>
 int launchTilesD(const TileFormatDev& t, int device, const uint16_t* A16, const uint16_t* B16, float* P, const Queue& s) {
     auto kernel = bsmr::denseTiles<KS, H, MODE, DEPTH>;
     const size_t lds = bsmr::tileLdsBytes(KS, H, DEPTH, t.entryCap);
     if (int st = raiseDynamicLds(reinterpret_cast<const void*>(kernel), lds, device)) return st;
 #ifdef BSMR_LAB_STAMPS
-    if (envInt("BSMR_TILE_STAMPS", 0)) {   // lab: one stamped launch, phase statistics on stderr
-        DevArray<uint64_t> dev;
-        const size_t n = (size_t)t.numItems * 8;
-        if (!allocOk(dev, n, "hipMalloc(stamps)")) return BSMR_ERR_HIP;
-        BSMR_HIP(hipMemset(dev, 0, n * 8));
-        hipLaunchKernelGGL(kernel, dim3(t.numItems, 1), dim3(bsmr::kWave), lds, s, A16, B16, t.groupRows, t.blockCols,
-                           reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P, t.entryCap,
-                           s.batch, dev);
-        BSMR_HIP(hipStreamSynchronize(s));
-        std::vector<uint64_t> h(n);
-        BSMR_HIP(hipMemcpy(h.data(), dev, n * 8, hipMemcpyDeviceToHost));
-        uint64_t first = ~0ull, last = 0;
-        for (uint32_t i = 0; i < t.numItems; ++i) {
-            first = std::min(first, h[(size_t)i * 8]);
-            last = std::max(last, h[(size_t)i * 8 + 4]);
-        }
-        auto med = [&](auto f) {
-            std::vector<double> v(t.numItems);
-            for (uint32_t i = 0; i < t.numItems; ++i) v[i] = f(&h[(size_t)i * 8]);
-            std::sort(v.begin(), v.end());
-            return std::make_pair(v[v.size() / 2], v[v.size() * 9 / 10]);
-        };
-        auto pr = [&](const char* name, std::pair<double, double> m) { fprintf(stderr, "  %-22s median %9.0f  p90 %9.0f\n", name, m.first, m.second); };
+    if (envInt("BSMR_TILE_STAMPS", 0)) {   // lab: one stamped launch, phase statistics on stderr (one record per item)
+        std::vector<uint64_t> h;
+        const int st = collectStamps(t.numItems, s, [&](uint64_t* stamps) {
+            hipLaunchKernelGGL(kernel, dim3(t.numItems, 1), dim3(bsmr::kWave), lds, s, A16, B16, t.groupRows, t.blockCols,
+                               reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P,
+                               t.entryCap, s.batch, stamps);
+        }, h);
+        if (st != BSMR_OK) return st;
+        uint64_t last = 0;
+        for (size_t i = 0; i < h.size(); i += 8) last = std::max(last, h[i + 4]);
         fprintf(stderr, "[tile stamps] KS=%d H=%d D=%d items=%u blocks=%llu lds=%zu span=%llu cycles (100 MHz ticks?)\n", KS, H, DEPTH,
-                t.numItems, (unsigned long long)t.numBlocks, lds, (unsigned long long)(last - first));
-        pr("start offset", med([&](const uint64_t* q) { return (double)(q[0] - first); }));
-        pr("prologue (meta)", med([&](const uint64_t* q) { return (double)(q[1] - q[0]); }));
-        pr("first image", med([&](const uint64_t* q) { return (double)(q[2] - q[1]); }));
-        pr("loop", med([&](const uint64_t* q) { return (double)(q[3] - q[2]); }));
-        pr("store drain", med([&](const uint64_t* q) { return (double)(q[4] - q[3]); }));
-        pr("  sum wait image", med([&](const uint64_t* q) { return (double)q[5]; }));
-        pr("  sum frag+mfma", med([&](const uint64_t* q) { return (double)q[6]; }));
-        pr("  sum slab+entries", med([&](const uint64_t* q) { return (double)q[7]; }));
-        pr("wave lifetime", med([&](const uint64_t* q) { return (double)(q[4] - q[0]); }));
+                t.numItems, (unsigned long long)t.numBlocks, lds, (unsigned long long)(last - firstStamp(h)));
+        printStamps(h, {{"start offset", 0, kStampFirst}, {"prologue (meta)", 1, 0}, {"first image", 2, 1}, {"loop", 3, 2},
+                        {"store drain", 4, 3}, {"  sum wait image", 5, kStampSum}, {"  sum frag+mfma", 6, kStampSum},
+                        {"  sum slab+entries", 7, kStampSum}, {"wave lifetime", 4, 0}}, 22);
         return BSMR_OK;
     }
     hipLaunchKernelGGL(kernel, dim3(t.numItems, s.batch.count), dim3(bsmr::kWave), lds, s, A16, B16, t.groupRows,
@@ -1093,35 +1179,18 @@ int launchSharedT(const TileFormatDev& t, int device, uint32_t numCols, const ui
         if (int st = raiseDynamicLds(reinterpret_cast<const void*>(kernel), lds, device)) return st;
 #ifdef BSMR_LAB_STAMPS
         if (envInt("BSMR_TILE_STAMPS", 0)) {   // lab: one stamped launch, phase statistics on stderr (one record per wave)
-            DevArray<uint64_t> dev;
-            const size_t nrec = (size_t)t.numItems * 4, n = nrec * 8;
-            if (!allocOk(dev, n, "hipMalloc(stamps)")) return BSMR_ERR_HIP;
-            BSMR_HIP(hipMemset(dev, 0, n * 8));
-            hipLaunchKernelGGL(kernel, dim3(t.numItems, 1), dim3(bsmr::kThreads), lds, s, A16, B16, t.groupRows, t.blockCols,
-                               reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P, numCols, s.batch, dev);
-            BSMR_HIP(hipStreamSynchronize(s));
-            std::vector<uint64_t> h(n);
-            BSMR_HIP(hipMemcpy(h.data(), dev, n * 8, hipMemcpyDeviceToHost));
-            uint64_t first = ~0ull;
-            for (size_t i = 0; i < nrec; ++i) first = std::min(first, h[i * 8]);
-            auto med = [&](auto f) {
-                std::vector<double> v(nrec);
-                for (size_t i = 0; i < nrec; ++i) v[i] = f(&h[i * 8]);
-                std::sort(v.begin(), v.end());
-                return std::make_pair(v[v.size() / 2], v[v.size() * 9 / 10]);
-            };
-            auto pr = [&](const char* name, std::pair<double, double> m) { fprintf(stderr, "  %-26s median %9.0f  p90 %9.0f\n", name, m.first, m.second); };
+            std::vector<uint64_t> h;
+            const int st = collectStamps((size_t)t.numItems * 4, s, [&](uint64_t* stamps) {
+                hipLaunchKernelGGL(kernel, dim3(t.numItems, 1), dim3(bsmr::kThreads), lds, s, A16, B16, t.groupRows, t.blockCols,
+                                   reinterpret_cast<const uint4*>(t.blockInfo.get()), t.entries, t.items, t.itemRowBase, P, numCols,
+                                   s.batch, stamps);
+            }, h);
+            if (st != BSMR_OK) return st;
             fprintf(stderr, "[shared stamps] KS=%d HW=%d items=%u blocks=%llu lds=%zu\n", KS, HW, t.numItems, (unsigned long long)t.numBlocks, lds);
-            pr("start offset", med([&](const uint64_t* q) { return (double)(q[0] - first); }));
-            pr("prologue (ids, rows)", med([&](const uint64_t* q) { return (double)(q[1] - q[0]); }));
-            pr("A fragments + step 0", med([&](const uint64_t* q) { return (double)(q[2] - q[1]); }));
-            pr("loop", med([&](const uint64_t* q) { return (double)(q[3] - q[2]); }));
-            pr("store drain", med([&](const uint64_t* q) { return (double)(q[4] - q[3]); }));
-            pr("  sum words+reads+mfma c0", med([&](const uint64_t* q) { return (double)q[5]; }));
-            pr("  sum rendezvous", med([&](const uint64_t* q) { return (double)q[6]; }));
-            pr("  sum gather+c1+writeback", med([&](const uint64_t* q) { return (double)q[7]; }));
-            pr("wave lifetime", med([&](const uint64_t* q) { return (double)(q[4] - q[0]); }));
-            pr("end offset", med([&](const uint64_t* q) { return (double)(q[4] - first); }));
+            printStamps(h, {{"start offset", 0, kStampFirst}, {"prologue (ids, rows)", 1, 0}, {"A fragments + step 0", 2, 1},
+                            {"loop", 3, 2}, {"store drain", 4, 3}, {"  sum words+reads+mfma c0", 5, kStampSum},
+                            {"  sum rendezvous", 6, kStampSum}, {"  sum gather+c1+writeback", 7, kStampSum},
+                            {"wave lifetime", 4, 0}, {"end offset", 4, kStampFirst}}, 26);
             return BSMR_OK;
         }
         hipLaunchKernelGGL(kernel, dim3(t.numItems, s.batch.count), dim3(bsmr::kThreads), lds, s, A16, B16, t.groupRows,
@@ -1274,21 +1343,21 @@ int launchSweepT(const SweepFormatDev& w, int device, uint32_t N, const void* A,
     return BSMR_OK;
 }
 
+// (PERCU = 1, one workgroup per CU: the item's entry words and the ring take most of its LDS)
 template <int KS, int PW, int MODE, bool SRC32>
-int launchSweepW(const SweepFormatDev& w, int device, uint32_t perCu, uint32_t N, const void* A, const void* B, float* P, const Queue& s) {
-    (void)perCu;   // (one workgroup per CU: the item's entry words and the ring take most of its LDS)
+int launchSweepW(const SweepFormatDev& w, int device, uint32_t N, const void* A, const void* B, float* P, const Queue& s) {
     if (w.W == 8) return launchSweepT<KS, PW, MODE, SRC32, 8, 1>(w, device, N, A, B, P, s);
     return launchSweepT<KS, PW, MODE, SRC32, 4, 1>(w, device, N, A, B, P, s);
 }
 
 template <int KS, int MODE, bool SRC32>
-int launchSweepP(const SweepFormatDev& w, int device, uint32_t perCu, uint32_t N, const void* A, const void* B, float* P, const Queue& s) {
+int launchSweepP(const SweepFormatDev& w, int device, uint32_t N, const void* A, const void* B, float* P, const Queue& s) {
     if constexpr (KS == 16) {
-        return w.PW == 1 ? launchSweepW<KS, 1, MODE, SRC32>(w, device, perCu, N, A, B, P, s)
-                         : launchSweepW<KS, 2, MODE, SRC32>(w, device, perCu, N, A, B, P, s);
+        return w.PW == 1 ? launchSweepW<KS, 1, MODE, SRC32>(w, device, N, A, B, P, s)
+                         : launchSweepW<KS, 2, MODE, SRC32>(w, device, N, A, B, P, s);
     } else {
-        return w.PW == 2 ? launchSweepW<KS, 2, MODE, SRC32>(w, device, perCu, N, A, B, P, s)
-                         : launchSweepW<KS, 4, MODE, SRC32>(w, device, perCu, N, A, B, P, s);
+        return w.PW == 2 ? launchSweepW<KS, 2, MODE, SRC32>(w, device, N, A, B, P, s)
+                         : launchSweepW<KS, 4, MODE, SRC32>(w, device, N, A, B, P, s);
     }
 }
 
@@ -1297,21 +1366,20 @@ template <int MODE>
 int launchSweep(const bsmr_plan* p, uint32_t K, const void* A, const void* B, float* P, const Queue& s, bool src32) {
     const SweepFormatDev& w = p->sweeps[(size_t)p->sweepNow];
     if (w.numItems == 0) return BSMR_OK;
-    const uint32_t perCu = sweepPerCu(p, w.W);
     if (src32) {
         switch (K) {
-        case 32: return launchSweepP<1, MODE, true>(w, p->device, perCu, p->N, A, B, P, s);
-        case 64: return launchSweepP<2, MODE, true>(w, p->device, perCu, p->N, A, B, P, s);
-        case 128: return launchSweepP<4, MODE, true>(w, p->device, perCu, p->N, A, B, P, s);
+        case 32: return launchSweepP<1, MODE, true>(w, p->device, p->N, A, B, P, s);
+        case 64: return launchSweepP<2, MODE, true>(w, p->device, p->N, A, B, P, s);
+        case 128: return launchSweepP<4, MODE, true>(w, p->device, p->N, A, B, P, s);
         default: return BSMR_ERR_INVALID_ARG;
         }
     }
     switch (K) {
-    case 32: return launchSweepP<1, MODE, false>(w, p->device, perCu, p->N, A, B, P, s);
-    case 64: return launchSweepP<2, MODE, false>(w, p->device, perCu, p->N, A, B, P, s);
-    case 128: return launchSweepP<4, MODE, false>(w, p->device, perCu, p->N, A, B, P, s);
-    case 256: return launchSweepP<8, MODE, false>(w, p->device, perCu, p->N, A, B, P, s);
-    case 512: return launchSweepP<16, MODE, false>(w, p->device, perCu, p->N, A, B, P, s);
+    case 32: return launchSweepP<1, MODE, false>(w, p->device, p->N, A, B, P, s);
+    case 64: return launchSweepP<2, MODE, false>(w, p->device, p->N, A, B, P, s);
+    case 128: return launchSweepP<4, MODE, false>(w, p->device, p->N, A, B, P, s);
+    case 256: return launchSweepP<8, MODE, false>(w, p->device, p->N, A, B, P, s);
+    case 512: return launchSweepP<16, MODE, false>(w, p->device, p->N, A, B, P, s);
     default: return BSMR_ERR_INVALID_ARG;
     }
 }
@@ -1534,24 +1602,12 @@ int launchDense16(const bsmr_plan* p, uint32_t K, const uint16_t* A16, const uin
     default: break;
     }
     const uint32_t wgs = (f.numItems + bsmr::kWavesPerWG - 1) / bsmr::kWavesPerWG;
-    if (f.tilesM)
-        hipLaunchKernelGGL((bsmr::denseGroupsAnyK<MODE, bsmr::TileMask>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A16,
-                           B16, K, f.H, f.groupRows, f.rowBase, f.blockCols, f.tilesM, f.blockMask, f.items,
-                           f.numItems, P, s.batch);
-    else if (f.tiles8)
-        hipLaunchKernelGGL((bsmr::denseGroupsAnyK<MODE, uint8_t>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A16,
-                           B16, K, f.H, f.groupRows, f.rowBase, f.blockCols, f.tiles8, f.blockMask, f.items,
-                           f.numItems, P, s.batch);
-    else if (f.tiles16)
-        hipLaunchKernelGGL((bsmr::denseGroupsAnyK<MODE, uint16_t>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A16,
-                           B16, K, f.H, f.groupRows, f.rowBase, f.blockCols, f.tiles16, f.blockMask, f.items,
-                           f.numItems, P, s.batch);
-    else
-        hipLaunchKernelGGL((bsmr::denseGroupsAnyK<MODE, uint32_t>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A16,
-                           B16, K, f.H, f.groupRows, f.rowBase, f.blockCols, f.tiles32, f.blockMask, f.items,
-                           f.numItems, P, s.batch);
-    BSMR_HIP(hipGetLastError());
-    return BSMR_OK;
+    return withTiles(f, [&](auto* tiles) {
+        hipLaunchKernelGGL((bsmr::denseGroupsAnyK<MODE, TileOf<decltype(tiles)>>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s,
+                           A16, B16, K, f.H, f.groupRows, f.rowBase, f.blockCols, tiles, f.blockMask, f.items, f.numItems, P, s.batch);
+        BSMR_HIP(hipGetLastError());
+        return BSMR_OK;
+    });
 }
 
 // fp32 operands, rounded to fp16 / bf16 in registers (small dense parts)
@@ -1581,20 +1637,12 @@ int launchDenseCvt(const bsmr_plan* p, uint32_t K, const float* A, const float* 
                         : launchStreamCvtT<4, MODE, uint8_t>(f, A, B, f.tiles8, P, s);
     }
     const uint32_t wgs = (f.numItems + bsmr::kWavesPerWG - 1) / bsmr::kWavesPerWG;
-    if (f.tilesM)
-        hipLaunchKernelGGL((bsmr::denseGroupsCvt<MODE, bsmr::TileMask>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K,
-                           f.H, f.groupRows, f.rowBase, f.blockCols, f.tilesM, f.blockMask, f.items, f.numItems, P, s.batch);
-    else if (f.tiles8)
-        hipLaunchKernelGGL((bsmr::denseGroupsCvt<MODE, uint8_t>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K,
-                           f.H, f.groupRows, f.rowBase, f.blockCols, f.tiles8, f.blockMask, f.items, f.numItems, P, s.batch);
-    else if (f.tiles16)
-        hipLaunchKernelGGL((bsmr::denseGroupsCvt<MODE, uint16_t>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K,
-                           f.H, f.groupRows, f.rowBase, f.blockCols, f.tiles16, f.blockMask, f.items, f.numItems, P, s.batch);
-    else
-        hipLaunchKernelGGL((bsmr::denseGroupsCvt<MODE, uint32_t>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K,
-                           f.H, f.groupRows, f.rowBase, f.blockCols, f.tiles32, f.blockMask, f.items, f.numItems, P, s.batch);
-    BSMR_HIP(hipGetLastError());
-    return BSMR_OK;
+    return withTiles(f, [&](auto* tiles) {
+        hipLaunchKernelGGL((bsmr::denseGroupsCvt<MODE, TileOf<decltype(tiles)>>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s,
+                           A, B, K, f.H, f.groupRows, f.rowBase, f.blockCols, tiles, f.blockMask, f.items, f.numItems, P, s.batch);
+        BSMR_HIP(hipGetLastError());
+        return BSMR_OK;
+    });
 }
 
 int launchDense32(const bsmr_plan* p, uint32_t K, const float* A, const float* B, float* P,
@@ -1602,20 +1650,12 @@ int launchDense32(const bsmr_plan* p, uint32_t K, const float* A, const float* B
     const DenseFormat& f = p->fmt[0];
     if (f.numItems == 0) return BSMR_OK;
     const uint32_t wgs = (f.numItems + bsmr::kWavesPerWG - 1) / bsmr::kWavesPerWG;
-    if (f.tilesM)
-        hipLaunchKernelGGL(bsmr::denseGroupsF32<bsmr::TileMask>, dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K, f.H,
-                           f.groupRows, f.rowBase, f.blockCols, f.tilesM, f.blockMask, f.items, f.numItems, P, s.batch);
-    else if (f.tiles8)
-        hipLaunchKernelGGL(bsmr::denseGroupsF32<uint8_t>, dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K, f.H,
-                           f.groupRows, f.rowBase, f.blockCols, f.tiles8, f.blockMask, f.items, f.numItems, P, s.batch);
-    else if (f.tiles16)
-        hipLaunchKernelGGL(bsmr::denseGroupsF32<uint16_t>, dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K, f.H,
-                           f.groupRows, f.rowBase, f.blockCols, f.tiles16, f.blockMask, f.items, f.numItems, P, s.batch);
-    else
-        hipLaunchKernelGGL(bsmr::denseGroupsF32<uint32_t>, dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K, f.H,
-                           f.groupRows, f.rowBase, f.blockCols, f.tiles32, f.blockMask, f.items, f.numItems, P, s.batch);
-    BSMR_HIP(hipGetLastError());
-    return BSMR_OK;
+    return withTiles(f, [&](auto* tiles) {
+        hipLaunchKernelGGL(bsmr::denseGroupsF32<TileOf<decltype(tiles)>>, dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B,
+                           K, f.H, f.groupRows, f.rowBase, f.blockCols, tiles, f.blockMask, f.items, f.numItems, P, s.batch);
+        BSMR_HIP(hipGetLastError());
+        return BSMR_OK;
+    });
 }
 
 // Lanes per entry of the residue kernels.  Tuned shapes (all of a lane's column chunks in
@@ -1801,10 +1841,26 @@ int reserve(bsmr_plan* p, uint32_t K) {
     return BSMR_OK;
 }
 
+// whether a hybrid call runs its residue kernel on the side stream: what bsmr_plan_tune measured, else as the plan was built
+inline bool overlapsResidue(const bsmr_plan* p) { return p->sideStream && (p->overlapNow >= 0 ? p->overlapNow == 1 : p->overlap); }
+
+// Hybrid call: the residue kernel on the side stream beside the dense kernel (the reference runs its two kernels on two
+// streams, src/sddmmKernel.cu:2555-2559, 2576, 2618).  Fork behind what the caller's stream holds (the conversion), join
+// on the caller's stream.  Entries are disjoint, operands read-only: no ordering between the two is needed.
+template <typename Side, typename Main>
+int forkJoin(const bsmr_plan* p, const Queue& s, Side&& runSide, Main&& runMain) {
+    BSMR_HIP(hipEventRecord(p->forkEvent, s));
+    BSMR_HIP(hipStreamWaitEvent(p->sideStream, p->forkEvent, 0));
+    if (int st = runSide(Queue(p->sideStream, s.batch))) return st;
+    BSMR_HIP(hipEventRecord(p->joinEvent, p->sideStream));
+    if (int st = runMain(s)) return st;
+    BSMR_HIP(hipStreamWaitEvent(s, p->joinEvent, 0));
+    return BSMR_OK;
+}
+
 // which: bit 0 convert, bit 1 dense, bit 2 sparse
 int runPieces(bsmr_plan* p, uint32_t K, const float* A, const float* B, float* P, int mode, const Queue& s,
               int which) {
-    const bool f16 = mode == BSMR_COMPUTE_F16;
     const bool hasDense = p->fmt[0].numItems != 0 || p->hostDense.entries() != 0;
     // what computes the dense part and the residue of this call
     enum { kNone, kDense32, kDenseCvt, kDense16 } dense = kNone;
@@ -1825,39 +1881,28 @@ int runPieces(bsmr_plan* p, uint32_t K, const float* A, const float* B, float* P
     if (!hasDense) dense = kNone;
     int st = BSMR_OK;
     if ((which & 1) && (convertAll || convertB)) {
-        st = f16 ? launchConvert<0>(p, K, A, B, p->A16, p->B16, s, convertB) : launchConvert<1>(p, K, A, B, p->A16, p->B16, s, convertB);
+        st = withMode(mode, [&](auto MODE) { return launchConvert<MODE()>(p, K, A, B, p->A16, p->B16, s, convertB); });
         if (st != BSMR_OK) return st;
     }
     auto runDense = [&](const Queue& q) -> int {
         switch (dense) {
         case kDense32: return launchDense32(p, K, A, B, P, q);
-        case kDenseCvt: return f16 ? launchDenseCvt<0>(p, K, A, B, P, q) : launchDenseCvt<1>(p, K, A, B, P, q);
-        case kDense16: return f16 ? launchDense16<0>(p, K, p->A16, p->B16, P, q) : launchDense16<1>(p, K, p->A16, p->B16, P, q);
+        case kDenseCvt: return withMode(mode, [&](auto MODE) { return launchDenseCvt<MODE()>(p, K, A, B, P, q); });
+        case kDense16: return withMode(mode, [&](auto MODE) { return launchDense16<MODE()>(p, K, p->A16, p->B16, P, q); });
         default: return BSMR_OK;
         }
     };
     auto runSparse = [&](const Queue& q) -> int {
         switch (sparse) {
-        case kSparse16: return f16 ? launchSparse16<0>(p, K, p->A16, p->B16, P, q) : launchSparse16<1>(p, K, p->A16, p->B16, P, q);
+        case kSparse16: return withMode(mode, [&](auto MODE) { return launchSparse16<MODE()>(p, K, p->A16, p->B16, P, q); });
         case kSparse16FromFp32A:
-            return f16 ? launchSparse16<0>(p, K, reinterpret_cast<const uint16_t*>(A), p->B16, P, q, true)
-                       : launchSparse16<1>(p, K, reinterpret_cast<const uint16_t*>(A), p->B16, P, q, true);
+            return withMode(mode, [&](auto MODE) {
+                return launchSparse16<MODE()>(p, K, reinterpret_cast<const uint16_t*>(A), p->B16, P, q, true);
+            });
         default: return launchSparse(p, K, A, B, P, q);
         }
     };
-    const bool overlap = p->sideStream && (p->overlapNow >= 0 ? p->overlapNow == 1 : p->overlap);
-    if ((which & 6) == 6 && overlap && dense != kNone && p->numSparseItems) {
-        // hybrid call: the residue kernel on the side stream beside the dense kernel (the reference runs its two
-        // kernels on two streams, src/sddmmKernel.cu:2555-2559, 2576, 2618).  Fork behind the conversion, join on
-        // the caller's stream.  Entries are disjoint, operands read-only: no ordering between the two is needed.
-        BSMR_HIP(hipEventRecord(p->forkEvent, s));
-        BSMR_HIP(hipStreamWaitEvent(p->sideStream, p->forkEvent, 0));
-        if ((st = runSparse(Queue(p->sideStream, s.batch))) != BSMR_OK) return st;
-        BSMR_HIP(hipEventRecord(p->joinEvent, p->sideStream));
-        if ((st = runDense(s)) != BSMR_OK) return st;
-        BSMR_HIP(hipStreamWaitEvent(s, p->joinEvent, 0));
-        return BSMR_OK;
-    }
+    if ((which & 6) == 6 && overlapsResidue(p) && dense != kNone && p->numSparseItems) return forkJoin(p, s, runSparse, runDense);
     if ((which & 2) && (st = runDense(s)) != BSMR_OK) return st;
     if ((which & 4) && (st = runSparse(s)) != BSMR_OK) return st;
     return BSMR_OK;
@@ -2700,9 +2745,9 @@ int bsmr_sddmm_batch(bsmr_plan* plan, uint32_t K, const float* A, const float* B
         // the batches are contiguous, so one conversion pass covers all of them
         if ((st = reserve(plan, K * num_batches)) != BSMR_OK) return st;
         const bool skipA = convertsBOnly(plan, K, num_batches);
-        st = mode == BSMR_COMPUTE_F16
-                 ? launchConvert<0>(plan, K * num_batches, A, B, plan->A16, plan->B16, Queue(s.stream), skipA)
-                 : launchConvert<1>(plan, K * num_batches, A, B, plan->A16, plan->B16, Queue(s.stream), skipA);
+        st = withMode(mode, [&](auto MODE) {
+            return launchConvert<MODE()>(plan, K * num_batches, A, B, plan->A16, plan->B16, Queue(s.stream), skipA);
+        });
         if (st != BSMR_OK) return st;
     }
     return runPieces(plan, K, A, B, P, mode, s, 6);  // dense + residue, grid y = batch
@@ -2728,9 +2773,9 @@ int bsmr_convert_operands(bsmr_plan* plan, uint32_t K, const float* A, const flo
     if (!aligned16(A) || !aligned16(B) || !aligned16(A16) || !aligned16(B16)) return BSMR_ERR_INVALID_ARG;
     BSMR_HIP(hipSetDevice(plan->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return mode == BSMR_COMPUTE_F16
-               ? launchConvert<0>(plan, K, A, B, static_cast<uint16_t*>(A16), static_cast<uint16_t*>(B16), s)
-               : launchConvert<1>(plan, K, A, B, static_cast<uint16_t*>(A16), static_cast<uint16_t*>(B16), s);
+    return withMode(mode, [&](auto MODE) {
+        return launchConvert<MODE()>(plan, K, A, B, static_cast<uint16_t*>(A16), static_cast<uint16_t*>(B16), s);
+    });
 }
 
 int bsmr_sddmm_lowp(bsmr_plan* plan, uint32_t K, const void* A16, const void* B16, const float* A,
@@ -2746,16 +2791,10 @@ int bsmr_sddmm_lowp(bsmr_plan* plan, uint32_t K, const void* A16, const void* B1
     BSMR_HIP(hipSetDevice(plan->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int pst = prepareDense(plan, K, mode)) return pst;
-    int st = mode == BSMR_COMPUTE_F16
-                 ? launchDense16<0>(plan, K, static_cast<const uint16_t*>(A16),
-                                    static_cast<const uint16_t*>(B16), P, s)
-                 : launchDense16<1>(plan, K, static_cast<const uint16_t*>(A16),
-                                    static_cast<const uint16_t*>(B16), P, s);
-    if (st != BSMR_OK) return st;
-    if (residueLowp)
-        return mode == BSMR_COMPUTE_F16
-                   ? launchSparse16<0>(plan, K, static_cast<const uint16_t*>(A16), static_cast<const uint16_t*>(B16), P, s)
-                   : launchSparse16<1>(plan, K, static_cast<const uint16_t*>(A16), static_cast<const uint16_t*>(B16), P, s);
+    const uint16_t* a = static_cast<const uint16_t*>(A16);
+    const uint16_t* b = static_cast<const uint16_t*>(B16);
+    if (int st = withMode(mode, [&](auto MODE) { return launchDense16<MODE()>(plan, K, a, b, P, s); })) return st;
+    if (residueLowp) return withMode(mode, [&](auto MODE) { return launchSparse16<MODE()>(plan, K, a, b, P, s); });
     return launchSparse(plan, K, A, B, P, s);
 }
 
@@ -2767,26 +2806,16 @@ static int runSddmm16(bsmr_plan* plan, uint32_t K, const void* A16, const void* 
     if (int st = prepareDense(plan, K, mode)) return st;
     const uint16_t* a = static_cast<const uint16_t*>(A16);
     const uint16_t* b = static_cast<const uint16_t*>(B16);
-    const bool f16 = mode == BSMR_COMPUTE_F16;
     auto runDense = [&](const Queue& q) -> int {
-        return f16 ? launchDense16<0>(plan, K, a, b, P, q) : launchDense16<1>(plan, K, a, b, P, q);
+        return withMode(mode, [&](auto MODE) { return launchDense16<MODE()>(plan, K, a, b, P, q); });
     };
     auto runSparse = [&](const Queue& q) -> int {
-        return f16 ? launchSparse16<0>(plan, K, a, b, P, q) : launchSparse16<1>(plan, K, a, b, P, q);
+        return withMode(mode, [&](auto MODE) { return launchSparse16<MODE()>(plan, K, a, b, P, q); });
     };
     const bool hasDense = plan->fmt[0].numItems != 0 || plan->hostDense.entries() != 0;
-    const bool overlap = plan->sideStream && (plan->overlapNow >= 0 ? plan->overlapNow == 1 : plan->overlap);
-    int st = BSMR_OK;
-    if (overlap && hasDense && plan->numSparseItems) {   // the fork / join of runPieces
-        BSMR_HIP(hipEventRecord(plan->forkEvent, s));
-        BSMR_HIP(hipStreamWaitEvent(plan->sideStream, plan->forkEvent, 0));
-        if ((st = runSparse(Queue(plan->sideStream, s.batch))) != BSMR_OK) return st;
-        BSMR_HIP(hipEventRecord(plan->joinEvent, plan->sideStream));
-        if ((st = runDense(s)) != BSMR_OK) return st;
-        BSMR_HIP(hipStreamWaitEvent(s, plan->joinEvent, 0));
-        return BSMR_OK;
-    }
-    if (hasDense && (st = runDense(s)) != BSMR_OK) return st;
+    if (overlapsResidue(plan) && hasDense && plan->numSparseItems) return forkJoin(plan, s, runSparse, runDense);
+    if (hasDense)
+        if (int st = runDense(s)) return st;
     return runSparse(s);
 }
 
@@ -2820,22 +2849,12 @@ int bsmr_sddmm_timed(bsmr_plan* plan, uint32_t K, const float* A, const float* B
     if ((st = prepareDense(plan, K, mode)) != BSMR_OK) return st;
     if (needsWorkspace(plan, mode, K) && (st = reserve(plan, K)) != BSMR_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    BSMR_HIP(hipEventCreate(&e0));
-    if (!hipOk(hipEventCreate(&e1), "hipEventCreate")) {
-        (void)hipEventDestroy(e0);
-        return BSMR_ERR_HIP;
-    }
+    EventPair ev;
+    if ((st = ev.create()) != BSMR_OK) return st;
     auto timeLoop = [&](int which, float& ms) -> int {
-        hipError_t e = hipEventRecord(e0, s);
-        int rc = BSMR_OK;
-        for (int i = 0; i < iters && rc == BSMR_OK; ++i) rc = runPieces(plan, K, A, B, P, mode, s, which);
-        if (e == hipSuccess) e = hipEventRecord(e1, s);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float t = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-        if (!hipOk(e, "event timing")) return BSMR_ERR_HIP;
-        ms = t / iters;
+        float us = 0.f;
+        const int rc = timedLoop(ev, s, iters, [&] { return runPieces(plan, K, A, B, P, mode, s, which); }, &us);
+        ms = us / 1000.f;
         return rc;
     };
     for (int i = 0; i < warmup && st == BSMR_OK; ++i) st = runPieces(plan, K, A, B, P, mode, s, 7);
@@ -2844,8 +2863,6 @@ int bsmr_sddmm_timed(bsmr_plan* plan, uint32_t K, const float* A, const float* B
     if (st == BSMR_OK && needsWorkspace(plan, mode, K)) st = timeLoop(1, t.convert_ms);
     if (st == BSMR_OK && plan->fmt[0].numItems) st = timeLoop(2, t.dense_ms);
     if (st == BSMR_OK && plan->numSparseItems) st = timeLoop(4, t.sparse_ms);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (st == BSMR_OK) *out = t;
     return st;
 }
@@ -2872,16 +2889,8 @@ int tuneEngines(bsmr_plan* plan, uint32_t K, const float* A, const float* B, flo
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t key = ((uint64_t)K << 8) | (uint32_t)mode;
     bsmr_plan::Tuned best;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    BSMR_HIP(hipEventCreate(&e0));
-    if (!hipOk(hipEventCreate(&e1), "hipEventCreate")) {
-        (void)hipEventDestroy(e0);
-        return BSMR_ERR_HIP;
-    }
-    struct Events {
-        hipEvent_t a, b;
-        ~Events() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-    } events{e0, e1};
+    EventPair ev;
+    if ((st = ev.create()) != BSMR_OK) return st;
     // microseconds per launch of the pieces `which` with the choice `c` (3 warm-up + 10 timed launches); < 0: c cannot run
     auto timeChoice = [&](const bsmr_plan::Tuned& c, int which, float& us) -> int {
         us = -1.f;
@@ -2895,19 +2904,11 @@ int tuneEngines(bsmr_plan* plan, uint32_t K, const float* A, const float* B, flo
         int rc = BSMR_OK;
         if (needsWorkspace(plan, mode, K) && (rc = reserve(plan, K)) != BSMR_OK) return rc;
         for (int i = 0; i < 3 && rc == BSMR_OK; ++i) rc = runPieces(plan, K, A, B, P, mode, s, which);
-        if (rc != BSMR_OK && !isRule) {
+        if (rc != BSMR_OK) {
             (void)hipStreamSynchronize(s);
-            return BSMR_OK;
+            return isRule ? rc : BSMR_OK;
         }
-        hipError_t e = hipEventRecord(e0, s);
-        for (int i = 0; i < 10 && rc == BSMR_OK; ++i) rc = runPieces(plan, K, A, B, P, mode, s, which);
-        if (e == hipSuccess) e = hipEventRecord(e1, s);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (!hipOk(e, "event timing")) return BSMR_ERR_HIP;
-        if (rc == BSMR_OK) us = ms * 100.f;
-        return rc;
+        return timedLoop(ev, s, 10, [&] { return runPieces(plan, K, A, B, P, mode, s, which); }, &us);
     };
     const bool lowp = mode != BSMR_COMPUTE_F32;
     // 1. the dense part: the streaming engine on either format, the tiles engine with its own rules, the shared-B engine
@@ -3102,27 +3103,17 @@ int tuneEngines(bsmr_plan* plan, uint32_t K, const float* A, const float* B, flo
 
 // whole calls of the plan as it is (its tuned choices included), microseconds per call
 int timeWholeCalls(bsmr_plan* plan, uint32_t K, const float* A, const float* B, float* P, int mode, hipStream_t s, float* us) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    BSMR_HIP(hipEventCreate(&e0));
-    if (!hipOk(hipEventCreate(&e1), "hipEventCreate")) {
-        (void)hipEventDestroy(e0);
-        return BSMR_ERR_HIP;
-    }
+    EventPair ev;
+    if (int est = ev.create()) return est;
     int st = BSMR_OK;
-    float best = 1e30f;
+    float best = 1e30f;   // the best of three repetitions of 3 warm-up + 30 timed calls
     for (int rep = 0; rep < 3 && st == BSMR_OK; ++rep) {
-        const int iters = 30;
         for (int i = 0; i < 3 && st == BSMR_OK; ++i) st = bsmr_sddmm(plan, K, A, B, P, mode, s);
         if (st != BSMR_OK) break;
-        (void)hipEventRecord(e0, s);
-        for (int i = 0; i < iters && st == BSMR_OK; ++i) st = bsmr_sddmm(plan, K, A, B, P, mode, s);
-        (void)hipEventRecord(e1, s);
-        if (!hipOk(hipEventSynchronize(e1), "hipEventSynchronize")) st = BSMR_ERR_HIP;
-        float ms = 0.f;
-        if (st == BSMR_OK && hipOk(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime")) best = std::min(best, ms * 1000.f / iters);
+        float t = best;
+        st = timedLoop(ev, s, 30, [&] { return bsmr_sddmm(plan, K, A, B, P, mode, s); }, &t);
+        best = std::min(best, t);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *us = best;
     return st;
 }
@@ -3402,15 +3393,10 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
         if (tableBytes > freeBytes / 2 || numBins * sizeof(uint32_t) > 160u * 1024u - 64u || bin_width > 65535u)
             return BSMR_ERR_OOM;
 
-        hipEvent_t ev0, ev1;
-        BSMR_HIP(hipEventCreate(&ev0));
-        BSMR_HIP(hipEventCreate(&ev1));
-        struct EventGuard {
-            hipEvent_t a, b;
-            ~EventGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
-        } guard{ev0, ev1};
+        EventPair ev;
+        if (int est = ev.create()) return est;
         hipStream_t s = nullptr;
-        BSMR_HIP(hipEventRecord(ev0, s));
+        BSMR_HIP(hipEventRecord(ev.start, s));
 
         DeviceBuffers dev;
         const uint32_t live = liveWarpMask(T);
@@ -3631,8 +3617,8 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
             for (uint32_t id = 1; id <= state.nextId; ++id) rank[id] = rank[id] ? ++used : 0;
             for (uint32_t p = firstNonEmpty; p < rows; ++p) cluster[p] = rank[cluster[p]];
         }
-        BSMR_HIP(hipEventRecord(ev1, s));
-        BSMR_HIP(hipEventSynchronize(ev1));
+        BSMR_HIP(hipEventRecord(ev.stop, s));
+        BSMR_HIP(hipEventSynchronize(ev.stop));
 
         // 4. stable sort of the positions by cluster id, logged count, empty rows dropped
         //    (src/rowReordering.cu:985-992, :1082-1090)
@@ -3652,7 +3638,7 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
         *num_reordered = out;
         if (stats) {
             float ms = 0.0f;
-            (void)hipEventElapsedTime(&ms, ev0, ev1);
+            (void)hipEventElapsedTime(&ms, ev.start, ev.stop);
             stats->elapsed_ms = ms;
             stats->passes = state.passes;
             stats->similarities = state.judged;

@@ -200,6 +200,60 @@ def test_spmm_x8_with_nan_and_infinity_rows(engine, oracle, pat, values, mode, f
     assert_twin(widen_words(mode, w)[0], oracle.round_array(ROUND[mode], twin), f"mode={mode} fmt={fmt}")
 
 
+class InPlacePattern:
+    """M = N = 96 on two handles: one created under BSMR_BACKWARD_PERMUTE=0, whose transposed gather reads v through
+    csc_to_csr (the MAP = true kernels; the C ABI takes transpose = 1 there, the torch operator does not), and one as by
+    default.  Row 40 has 600 entries, 520 of them in column 7 - a CSR may name a column twice, every entry has its own
+    value - so one list of either direction is cut into two chunks and the reduce runs; the other rows have 1 - 3."""
+
+    def __init__(self, engine):
+        rng = np.random.default_rng(5)
+        self.engine, self.rows, self.cols = engine, 96, 96
+        per_row = [np.sort(rng.choice(96, int(rng.integers(1, 4)), replace=False)) for _ in range(96)]
+        per_row[40] = rng.permutation(np.concatenate([np.full(520, 7), rng.integers(0, 96, 80)]))
+        self.ro = np.zeros(97, dtype=np.uint32)
+        self.ro[1:] = np.cumsum([a.size for a in per_row])
+        self.ci = np.concatenate(per_row).astype(np.uint32)
+        self.nnz = int(self.ci.size)
+        self.permuted = engine.backward_create(96, 96, self.ro, self.ci, device=0)
+        with pytest.MonkeyPatch.context() as mp:                             # read at create
+            mp.setenv("BSMR_BACKWARD_PERMUTE", "0")
+            self.bw = engine.backward_create(96, 96, self.ro, self.ci, device=0)
+        for bw, permute in ((self.bw, 0), (self.permuted, 1)):
+            st = engine.backward_stats(bw)
+            assert (st["permute_values"], st["split_rows"], st["split_cols"]) == (permute, 1, 1)
+            assert st["max_row_length"] == 600 and st["chunk"] < st["max_col_length"] < 2 * st["chunk"]
+
+    def close(self):
+        self.engine.backward_destroy(self.bw)
+        self.engine.backward_destroy(self.permuted)
+
+
+@pytest.fixture(scope="module")
+def in_place(engine):
+    p = InPlacePattern(engine)
+    yield p
+    p.close()
+
+
+@pytest.mark.parametrize("K", (32, 96, 256))
+def test_spmm_x8_in_place_is_spmm_16_on_the_widened_rows(engine, in_place, K):
+    """BSMR_BACKWARD_PERMUTE=0 with transpose = 1 is spmmGather8<.., MAP = true>: bit for bit bsmr_spmm_16 on the widened
+    copy and the call on the permuting handle, over direct and split lists, one slice, three slices and the widest slice"""
+    p, nb = in_place, 2
+    rng = np.random.default_rng(900 + K)
+    v = _wide(rng, (nb, p.nnz), -3, 3)
+    for mode, fmt in COMBOS:
+        X8 = finite_codes(rng, fmt, (nb, 96, K))
+        for transpose in (1, 0):
+            where = f"in place: fmt={fmt} mode={mode} transpose={transpose} K={K}"
+            w = dev_spmm8(engine, p.bw, p, K, transpose, v, X8, mode, fmt, nb)
+            w16 = dev_spmm16(engine, p.bw, p, K, transpose, v, widen16(mode, fmt, X8), mode, nb)
+            assert w.any() and w.tobytes() == w16.tobytes(), where + ": differs from bsmr_spmm_16 on the widened copy"
+            wp = dev_spmm8(engine, p.permuted, p, K, transpose, v, X8, mode, fmt, nb)
+            assert w.tobytes() == wp.tobytes(), where + ": differs from the handle that permutes v"
+
+
 # ---- 3. the fused attention --------------------------------------------------------------------------------------------
 def dev_attention(engine, bw, p, Kv, scale, scores, V, nb, mode, fmt=None):
     """V: uint8 codes (fmt given), a 16-bit CPU tensor, or fp32 numpy (mode None) -> (O words or fp32, m, s) as numpy"""

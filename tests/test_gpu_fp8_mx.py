@@ -19,7 +19,8 @@ import pytest
 from attention_twin import check_forward
 from gather_twin import assert_twin, gather
 from guarded import OPERAND, VALUES, Guarded, check_all
-from test_gpu_fp8 import COMBOS, F8, dev_attention, dev_sddmm, dev_spmm8, dev_spmm16, finite_codes, int_codes, small_ints
+from test_gpu_fp8 import (COMBOS, F8, dev_attention, dev_sddmm, dev_spmm8, dev_spmm16, finite_codes, in_place, int_codes,  # noqa: F401
+                          small_ints)
 from test_gpu_io16 import DT, EMPTY_COL, NB, ROUND, Pattern, _wide, to16, widen_words, words
 from test_gpu_numerics import DENSE_PATS, _build, assert_exact, model, patterns  # noqa: F401 (fixture)
 
@@ -208,6 +209,29 @@ def test_spmm_x8_mx_equals_the_rounded_twin(engine, oracle, pat, values, fmt, K)
                 w1 = dev_spmm8_mx(engine, bw, pat, K, transpose, values, X8, ones, mode, fmt, nb)
                 w8 = dev_spmm8(engine, bw, pat, K, transpose, values, X8, mode, fmt, nb)
                 assert w1.tobytes() == w8.tobytes(), where + ": scale code 127 is not bsmr_spmm_x8"
+
+
+@pytest.mark.parametrize("K", (32, 96, 256))
+def test_spmm_x8_mx_in_place_is_spmm_on_dq(engine, in_place, K):
+    """BSMR_BACKWARD_PERMUTE=0 with transpose = 1 is spmmGather8<.., MAP = true, .., MX = true>: bit for bit bsmr_spmm on dq
+    narrowed, bsmr_spmm_16 on the 16-bit copy of dq where that copy is exact, and the call on the permuting handle"""
+    p, nb = in_place, 2
+    rng = np.random.default_rng(950 + K)
+    v = _wide(rng, (nb, p.nnz), -3, 3)
+    for mode, fmt in COMBOS:
+        X8 = finite_codes(rng, fmt, (nb, 96, K))
+        E8 = scale_codes((nb, 96, K // 32), salt=K + fmt)
+        X = dq32(fmt, X8, E8)
+        for transpose in (1, 0):
+            where = f"in place: fmt={fmt} mode={mode} transpose={transpose} K={K}"
+            w = dev_spmm8_mx(engine, p.bw, p, K, transpose, v, X8, E8, mode, fmt, nb)
+            Y32 = dev_spmm32(engine, p.bw, p, K, transpose, v, X, nb)
+            assert w.any() and w.tobytes() == words(to16(mode, Y32)).tobytes(), where + ": not bsmr_spmm on dq narrowed"
+            if copy_is_exact(mode, X):
+                w16 = dev_spmm16(engine, p.bw, p, K, transpose, v, to16(mode, X), mode, nb)
+                assert w.tobytes() == w16.tobytes(), where + ": differs from bsmr_spmm_16 on the dequantised copy"
+            wp = dev_spmm8_mx(engine, p.permuted, p, K, transpose, v, X8, E8, mode, fmt, nb)
+            assert w.tobytes() == wp.tobytes(), where + ": differs from the handle that permutes v"
 
 
 @pytest.mark.parametrize("mode,fmt", COMBOS)
