@@ -1574,6 +1574,19 @@ inline bool tilesEngine(const bsmr_plan* p, uint32_t K) {
     return !gemmEngine(p) && !sweepEngine(p) && p->useTiles && tilesServeK(K) && p->hostDense.entries() != 0 && !cvtInKernel(p, K);
 }
 
+// The any-K dense fallbacks (denseGroupsAnyK, denseGroupsCvt, denseGroupsF32: one body, csrc/sddmm_kernels.hpp denseAnyK):
+// one wave per item.  kernelOf(tiles) names the kernel for the plan's tile encoding.
+template <typename T, typename KernelOf>
+int launchAnyK(const DenseFormat& f, uint32_t K, const T* A, const T* B, float* P, const Queue& s, KernelOf kernelOf) {
+    const uint32_t wgs = (f.numItems + bsmr::kWavesPerWG - 1) / bsmr::kWavesPerWG;
+    return withTiles(f, [&](auto* tiles) {
+        hipLaunchKernelGGL(kernelOf(tiles), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B, K, f.H, f.groupRows, f.rowBase,
+                           f.blockCols, tiles, f.blockMask, f.items, f.numItems, P, s.batch);
+        BSMR_HIP(hipGetLastError());
+        return BSMR_OK;
+    });
+}
+
 template <int MODE>
 int launchDense16(const bsmr_plan* p, uint32_t K, const uint16_t* A16, const uint16_t* B16, float* P,
                   const Queue& s) {
@@ -1601,13 +1614,7 @@ int launchDense16(const bsmr_plan* p, uint32_t K, const uint16_t* A16, const uin
     case 512: return launchGroupsH<16, 2, MODE>(f, A16, B16, P, s);
     default: break;
     }
-    const uint32_t wgs = (f.numItems + bsmr::kWavesPerWG - 1) / bsmr::kWavesPerWG;
-    return withTiles(f, [&](auto* tiles) {
-        hipLaunchKernelGGL((bsmr::denseGroupsAnyK<MODE, TileOf<decltype(tiles)>>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s,
-                           A16, B16, K, f.H, f.groupRows, f.rowBase, f.blockCols, tiles, f.blockMask, f.items, f.numItems, P, s.batch);
-        BSMR_HIP(hipGetLastError());
-        return BSMR_OK;
-    });
+    return launchAnyK(f, K, A16, B16, P, s, [](auto* tiles) { return bsmr::denseGroupsAnyK<MODE, TileOf<decltype(tiles)>>; });
 }
 
 // fp32 operands, rounded to fp16 / bf16 in registers (small dense parts)
@@ -1636,26 +1643,14 @@ int launchDenseCvt(const bsmr_plan* p, uint32_t K, const float* A, const float* 
         return f.tilesM ? launchStreamCvtT<4, MODE, bsmr::TileMask>(f, A, B, f.tilesM, P, s)
                         : launchStreamCvtT<4, MODE, uint8_t>(f, A, B, f.tiles8, P, s);
     }
-    const uint32_t wgs = (f.numItems + bsmr::kWavesPerWG - 1) / bsmr::kWavesPerWG;
-    return withTiles(f, [&](auto* tiles) {
-        hipLaunchKernelGGL((bsmr::denseGroupsCvt<MODE, TileOf<decltype(tiles)>>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s,
-                           A, B, K, f.H, f.groupRows, f.rowBase, f.blockCols, tiles, f.blockMask, f.items, f.numItems, P, s.batch);
-        BSMR_HIP(hipGetLastError());
-        return BSMR_OK;
-    });
+    return launchAnyK(f, K, A, B, P, s, [](auto* tiles) { return bsmr::denseGroupsCvt<MODE, TileOf<decltype(tiles)>>; });
 }
 
 int launchDense32(const bsmr_plan* p, uint32_t K, const float* A, const float* B, float* P,
                   const Queue& s) {
     const DenseFormat& f = p->fmt[0];
     if (f.numItems == 0) return BSMR_OK;
-    const uint32_t wgs = (f.numItems + bsmr::kWavesPerWG - 1) / bsmr::kWavesPerWG;
-    return withTiles(f, [&](auto* tiles) {
-        hipLaunchKernelGGL(bsmr::denseGroupsF32<TileOf<decltype(tiles)>>, dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B,
-                           K, f.H, f.groupRows, f.rowBase, f.blockCols, tiles, f.blockMask, f.items, f.numItems, P, s.batch);
-        BSMR_HIP(hipGetLastError());
-        return BSMR_OK;
-    });
+    return launchAnyK(f, K, A, B, P, s, [](auto* tiles) { return bsmr::denseGroupsF32<TileOf<decltype(tiles)>>; });
 }
 
 // Lanes per entry of the residue kernels.  Tuned shapes (all of a lane's column chunks in
@@ -1677,80 +1672,81 @@ SparseShape sparseShape(const bsmr_plan* p, uint32_t K, bool lowp) {
     return {lpe, 0};
 }
 
-template <int LPE, int CPL>
-int launchSparseT(const bsmr_plan* p, uint32_t K, const float* A, const float* B, float* P, const Queue& s) {
-    const size_t lds = (size_t)16 * (K + bsmr::kSparseLdsPad) * sizeof(float);
-    const uint32_t wgs = p->numSparseItems;  // no padding: every workgroup reads its item
-    if (p->sparseFree) {
-        hipLaunchKernelGGL((bsmr::sparseEntries<LPE, false, CPL, true>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s,
-                           A, B, K, p->entryRowId, p->entryCol, p->entryDst, p->entryRow, p->sparseItems, P, s.batch);
-    } else if (lds <= 64 * 1024) {
-        hipLaunchKernelGGL((bsmr::sparseEntries<LPE, true, CPL>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), lds, s, A, B,
-                           K, p->panelRows, p->entryCol, p->entryDst, p->entryRow, p->sparseItems, P, s.batch);
-    } else {
-        hipLaunchKernelGGL((bsmr::sparseEntries<LPE, false, CPL>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s, A, B,
-                           K, p->panelRows, p->entryCol, p->entryDst, p->entryRow, p->sparseItems, P, s.batch);
-    }
-    BSMR_HIP(hipGetLastError());
-    return BSMR_OK;
-}
+// LDS bytes of a staged panel: 16 A rows of K elements, each padded (csrc/sddmm_kernels.hpp residueEntries)
+inline size_t panelLdsBytes(uint32_t K, size_t elemBytes) { return (size_t)16 * (K * elemBytes + bsmr::kSparseLdsPad); }
+inline bool panelFitsLds(uint32_t K, size_t elemBytes) { return panelLdsBytes(K, elemBytes) <= 64 * 1024; }
 
-int launchSparse(const bsmr_plan* p, uint32_t K, const float* A, const float* B, float* P, const Queue& s) {
-    if (p->numSparseItems == 0) return BSMR_OK;
-    const SparseShape sh = sparseShape(p, K, false);
-    switch (sh.lpe * 100 + sh.cpl) {
-    case 402: return launchSparseT<4, 2>(p, K, A, B, P, s);    // K = 32
-    case 404: return launchSparseT<4, 4>(p, K, A, B, P, s);    // K = 64
-    case 804: return launchSparseT<8, 4>(p, K, A, B, P, s);    // K = 128
-    case 808: return launchSparseT<8, 8>(p, K, A, B, P, s);    // K = 256
-    case 1608: return launchSparseT<16, 8>(p, K, A, B, P, s);  // K = 512
-    case 1600: return launchSparseT<16, 0>(p, K, A, B, P, s);
-    case 400: return launchSparseT<4, 0>(p, K, A, B, P, s);
-    default: return launchSparseT<8, 0>(p, K, A, B, P, s);
+// The two residue kernel families: the operand type and the kernel of a shape (LPE, CPL) in a form (A_IN_LDS, FREE, A_FP32)
+struct Residue32 {
+    typedef float elem;
+    static constexpr bool lowp = false;
+    template <int LPE, int CPL, bool A_IN_LDS, bool FREE, bool A_FP32>
+    static auto kernel() {
+        static_assert(!A_FP32, "only the 16-bit residue rounds A");
+        return bsmr::sparseEntries<LPE, A_IN_LDS, CPL, FREE>;
     }
-}
-
-template <int LPE, int CPL, int MODE>
-int launchSparse16T(const bsmr_plan* p, uint32_t K, const uint16_t* A16, const uint16_t* B16, float* P,
-                    const Queue& s, bool aFp32) {
-    const size_t lds = (size_t)16 * (2u * K + bsmr::kSparseLdsPad16);
-    const uint32_t wgs = p->numSparseItems;
-    if (aFp32) {  // only set when the panels fit LDS and the residue is in panel form
-        hipLaunchKernelGGL((bsmr::sparseEntriesLowp<LPE, MODE, true, CPL, false, true>), dim3(wgs, s.batch.count),
-                           dim3(bsmr::kThreads), lds, s, A16, B16, K, p->panelRows, p->entryCol, p->entryDst, p->entryRow,
-                           p->sparseItems, P, s.batch);
-    } else if (p->sparseFree) {
-        hipLaunchKernelGGL((bsmr::sparseEntriesLowp<LPE, MODE, false, CPL, true>), dim3(wgs, s.batch.count),
-                           dim3(bsmr::kThreads), 0, s, A16, B16, K, p->entryRowId, p->entryCol, p->entryDst, p->entryRow,
-                           p->sparseItems, P, s.batch);
-    } else if (lds <= 64 * 1024) {
-        hipLaunchKernelGGL((bsmr::sparseEntriesLowp<LPE, MODE, true, CPL>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), lds, s,
-                           A16, B16, K, p->panelRows, p->entryCol, p->entryDst, p->entryRow, p->sparseItems, P, s.batch);
-    } else {
-        hipLaunchKernelGGL((bsmr::sparseEntriesLowp<LPE, MODE, false, CPL>), dim3(wgs, s.batch.count), dim3(bsmr::kThreads), 0, s,
-                           A16, B16, K, p->panelRows, p->entryCol, p->entryDst, p->entryRow, p->sparseItems, P, s.batch);
-    }
-    BSMR_HIP(hipGetLastError());
-    return BSMR_OK;
-}
-
-// aFp32: A16 is the caller's fp32 A (plans that convert B alone)
+};
 template <int MODE>
-int launchSparse16(const bsmr_plan* p, uint32_t K, const uint16_t* A16, const uint16_t* B16, float* P,
-                   const Queue& s, bool aFp32 = false) {
-    if (p->numSparseItems == 0) return BSMR_OK;
-    const SparseShape sh = sparseShape(p, K, true);
-    switch (sh.lpe * 100 + sh.cpl) {
-    case 401: return launchSparse16T<4, 1, MODE>(p, K, A16, B16, P, s, aFp32);  // K = 32
-    case 402: return launchSparse16T<4, 2, MODE>(p, K, A16, B16, P, s, aFp32);  // K = 64
-    case 404: return launchSparse16T<4, 4, MODE>(p, K, A16, B16, P, s, aFp32);  // K = 128
-    case 804: return launchSparse16T<8, 4, MODE>(p, K, A16, B16, P, s, aFp32);  // K = 256
-    case 808: return launchSparse16T<8, 8, MODE>(p, K, A16, B16, P, s, aFp32);  // K = 512
-    case 1600: return launchSparse16T<16, 0, MODE>(p, K, A16, B16, P, s, aFp32);
-    case 400: return launchSparse16T<4, 0, MODE>(p, K, A16, B16, P, s, aFp32);
-    default: return launchSparse16T<8, 0, MODE>(p, K, A16, B16, P, s, aFp32);
+struct Residue16 {
+    typedef uint16_t elem;
+    static constexpr bool lowp = true;
+    template <int LPE, int CPL, bool A_IN_LDS, bool FREE, bool A_FP32>
+    static auto kernel() { return bsmr::sparseEntriesLowp<LPE, MODE, A_IN_LDS, CPL, FREE, A_FP32>; }
+};
+
+// aFp32 (16-bit only): A is the caller's fp32 A, rounded while the panel is staged - only set when the panels fit LDS and
+// the residue is in panel form (convertsBOnly)
+template <typename F, int LPE, int CPL>
+int launchResidueT(const bsmr_plan* p, uint32_t K, const typename F::elem* A, const typename F::elem* B, float* P, const Queue& s,
+                   bool aFp32) {
+    const size_t lds = panelLdsBytes(K, sizeof(typename F::elem));
+    auto launch = [&](auto kernel, size_t ldsBytes, const uint32_t* rows) {
+        // no padding of the grid: every workgroup reads its item
+        hipLaunchKernelGGL(kernel, dim3(p->numSparseItems, s.batch.count), dim3(bsmr::kThreads), ldsBytes, s, A, B, K, rows, p->entryCol,
+                           p->entryDst, p->entryRow, p->sparseItems, P, s.batch);
+    };
+    if (aFp32) {
+        if constexpr (F::lowp) launch(F::template kernel<LPE, CPL, true, false, true>(), lds, p->panelRows);
+        else return BSMR_ERR_INVALID_ARG;
+    } else if (p->sparseFree) {
+        launch(F::template kernel<LPE, CPL, false, true, false>(), 0, p->entryRowId);
+    } else if (panelFitsLds(K, sizeof(typename F::elem))) {
+        launch(F::template kernel<LPE, CPL, true, false, false>(), lds, p->panelRows);
+    } else {
+        // a tuned shape is never unstaged in panel form: it exists for K <= 512, whose panel (33 024 bytes of fp32,
+        // 16 640 of 16-bit) always fits, so those kernels are not instantiated
+        if constexpr (CPL == 0) launch(F::template kernel<LPE, 0, false, false, false>(), 0, p->panelRows);
+        else return BSMR_ERR_INVALID_ARG;
     }
+    BSMR_HIP(hipGetLastError());
+    return BSMR_OK;
 }
+
+// F: Residue32 or Residue16<MODE>.  Each family instantiates the tuned shapes it takes (sparseShape) and no others.
+template <typename F>
+int launchResidue(const bsmr_plan* p, uint32_t K, const typename F::elem* A, const typename F::elem* B, float* P, const Queue& s,
+                  bool aFp32 = false) {
+    if (p->numSparseItems == 0) return BSMR_OK;
+    const SparseShape sh = sparseShape(p, K, F::lowp);
+    auto shape = [&](auto LPE, auto CPL) { return launchResidueT<F, LPE(), CPL()>(p, K, A, B, P, s, aFp32); };
+    switch (sh.lpe * 100 + sh.cpl) {   // tuned: K = 4 * LPE * CPL in fp32, 8 * LPE * CPL in 16 bits
+    case 401:                                                                         // 16-bit K = 32
+        if constexpr (F::lowp) return shape(Int<4>(), Int<1>());
+        break;
+    case 402: return shape(Int<4>(), Int<2>());  // fp32 K = 32, 16-bit K = 64
+    case 404: return shape(Int<4>(), Int<4>());  // fp32 K = 64, 16-bit K = 128
+    case 804: return shape(Int<8>(), Int<4>());  // fp32 K = 128, 16-bit K = 256
+    case 808: return shape(Int<8>(), Int<8>());  // fp32 K = 256, 16-bit K = 512
+    case 1608:                                                                        // fp32 K = 512
+        if constexpr (!F::lowp) return shape(Int<16>(), Int<8>());
+        break;
+    case 1600: return shape(Int<16>(), Int<0>());
+    case 400: return shape(Int<4>(), Int<0>());
+    default: break;
+    }
+    return shape(Int<8>(), Int<0>());
+}
+
 
 int checkCall(const bsmr_plan* p, uint32_t K, const void* A, const void* B, const void* P, int mode) {
     if (!p || !P) return BSMR_ERR_INVALID_ARG;
@@ -1777,7 +1773,7 @@ int checkDeviceCall(const bsmr_plan* p, uint32_t K, const void* A, const void* B
 // all-sparse plan, residue entries x K large enough to repay a conversion pass over B (and the kernel boundary
 // after it): B alone is converted and the residue kernel rounds A's rows while it stages them in LDS
 inline bool convertsBOnly(const bsmr_plan* p, uint32_t K, uint32_t batches = 1) {
-    if (!p->convertBOnly || (size_t)16 * (2u * K + bsmr::kSparseLdsPad16) > 64 * 1024) return false;
+    if (!p->convertBOnly || !panelFitsLds(K, sizeof(uint16_t))) return false;
     if (p->bOnlyNow >= 0) return p->bOnlyNow == 1;   // measured (bsmr_plan_tune)
     const uint64_t work = (uint64_t)p->numSparseEntries * K * batches;
     // the pass costs ~N*K, the halved gather saves ~entries*K: patterns with >= 11 entries per column repay it from
@@ -1894,12 +1890,12 @@ int runPieces(bsmr_plan* p, uint32_t K, const float* A, const float* B, float* P
     };
     auto runSparse = [&](const Queue& q) -> int {
         switch (sparse) {
-        case kSparse16: return withMode(mode, [&](auto MODE) { return launchSparse16<MODE()>(p, K, p->A16, p->B16, P, q); });
+        case kSparse16: return withMode(mode, [&](auto MODE) { return launchResidue<Residue16<MODE()>>(p, K, p->A16, p->B16, P, q); });
         case kSparse16FromFp32A:
             return withMode(mode, [&](auto MODE) {
-                return launchSparse16<MODE()>(p, K, reinterpret_cast<const uint16_t*>(A), p->B16, P, q, true);
+                return launchResidue<Residue16<MODE()>>(p, K, reinterpret_cast<const uint16_t*>(A), p->B16, P, q, true);
             });
-        default: return launchSparse(p, K, A, B, P, q);
+        default: return launchResidue<Residue32>(p, K, A, B, P, q);
         }
     };
     if ((which & 6) == 6 && overlapsResidue(p) && dense != kNone && p->numSparseItems) return forkJoin(p, s, runSparse, runDense);
@@ -2794,8 +2790,8 @@ int bsmr_sddmm_lowp(bsmr_plan* plan, uint32_t K, const void* A16, const void* B1
     const uint16_t* a = static_cast<const uint16_t*>(A16);
     const uint16_t* b = static_cast<const uint16_t*>(B16);
     if (int st = withMode(mode, [&](auto MODE) { return launchDense16<MODE()>(plan, K, a, b, P, s); })) return st;
-    if (residueLowp) return withMode(mode, [&](auto MODE) { return launchSparse16<MODE()>(plan, K, a, b, P, s); });
-    return launchSparse(plan, K, A, B, P, s);
+    if (residueLowp) return withMode(mode, [&](auto MODE) { return launchResidue<Residue16<MODE()>>(plan, K, a, b, P, s); });
+    return launchResidue<Residue32>(plan, K, A, B, P, s);
 }
 
 // The body of bsmr_sddmm_16 behind its checks (plan: the served plan, its device current; num_batches >= 1): shared with
@@ -2810,7 +2806,7 @@ static int runSddmm16(bsmr_plan* plan, uint32_t K, const void* A16, const void* 
         return withMode(mode, [&](auto MODE) { return launchDense16<MODE()>(plan, K, a, b, P, q); });
     };
     auto runSparse = [&](const Queue& q) -> int {
-        return withMode(mode, [&](auto MODE) { return launchSparse16<MODE()>(plan, K, a, b, P, q); });
+        return withMode(mode, [&](auto MODE) { return launchResidue<Residue16<MODE()>>(plan, K, a, b, P, q); });
     };
     const bool hasDense = plan->fmt[0].numItems != 0 || plan->hostDense.entries() != 0;
     if (overlapsResidue(plan) && hasDense && plan->numSparseItems) return forkJoin(plan, s, runSparse, runDense);
@@ -2820,7 +2816,7 @@ static int runSddmm16(bsmr_plan* plan, uint32_t K, const void* A16, const void* 
 }
 
 // The forward on 16-bit operands alone: every engine's 16-bit kernel (launchDense16) and the 16-bit residue kernel
-// (launchSparse16), whatever the plan says about the road its fp32 operands take.  Both read formats that do not
+// (launchResidue), whatever the plan says about the road its fp32 operands take.  Both read formats that do not
 // depend on that road: the GEMM and sweep formats are keyed by their shape alone (the fp32-operand GEMM kernels are
 // built for a subset of the 16-bit kernels' shapes) and size their LDS per launch from the operand type; a plan that
 // rounds in the streaming kernel keeps the streaming format launchStream reads; the tiles engine is only prepared
@@ -2976,7 +2972,7 @@ int tuneEngines(bsmr_plan* plan, uint32_t K, const float* A, const float* B, flo
         }
     }
     // 2. plans without a dense part: the fp32 residue kernel against converting B alone and reading 16-bit operands
-    if (st == BSMR_OK && lowp && plan->convertBOnly && (size_t)16 * (2u * K + bsmr::kSparseLdsPad16) <= 64 * 1024) {
+    if (st == BSMR_OK && lowp && plan->convertBOnly && panelFitsLds(K, sizeof(uint16_t))) {
         bsmr_plan::Tuned c = best;
         c.bOnly = 0;
         st = timeChoice(c, 7, r.fp32_residue_us);

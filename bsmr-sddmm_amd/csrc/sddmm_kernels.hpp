@@ -29,10 +29,15 @@
 //    absolute 32-bit indices per block).  Tiles without entries are skipped
 //    through a per-block bit mask.  Layouts: csrc/plan_pack.hpp.
 //
-// Sparse residue (sparseEntries): K split over LPE lanes per entry (coalesced
-// 16-byte loads of the B column), A rows from LDS, butterfly reduction; exact
-// fp32 with a defined summation order (bit-level CPU twin:
-// oracle/sddmm_oracle.c oracle_sparse_twin).
+// Dense fallbacks for any K (denseGroupsAnyK, denseGroupsCvt, denseGroupsF32): one
+// body, denseAnyK, over a fragment policy (16-bit, fp32 rounded in registers,
+// exact fp32).
+//
+// Sparse residue (sparseEntries, sparseEntriesLowp): one body, residueEntries,
+// over an element policy (fp32, or the fp16 / bf16 copies).  K split over LPE
+// lanes per entry (coalesced 16-byte loads of the B column), A rows from LDS,
+// butterfly reduction; in fp32 exact with a defined summation order (bit-level
+// CPU twin: oracle/sddmm_oracle.c oracle_sparse_twin).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -728,9 +733,88 @@ denseStreamCvt(const float* __restrict__ A, const float* __restrict__ B, const u
 }
 
 // ---------------------------------------------------------------------------
-// dense fallback, 16-bit operands, any K (multiple of 32): fragments straight
-// from global memory, run-time K loop.  One wave per DenseItem.
+// dense fallbacks for any K (multiple of 32): one wave per DenseItem, fragments straight from global memory, run-time
+// K loop.  One body (denseAnyK); a fragment policy says what a lane loads and what one K step does with it:
+//   elem   operand type
+//   kLane  element offset of lane group g inside a step (g * kLane)
+//   kStep  K covered per step
+//   step   acc += (fragment s of the A row) x (fragment s of the B column)
 // ---------------------------------------------------------------------------
+template <int MODE>  // 16-bit operands
+struct Frag16 {
+    typedef uint16_t elem;
+    static constexpr uint32_t kLane = 8, kStep = 32;
+    static __device__ __forceinline__ f32x4 step(const elem* aRow, const elem* bCol, uint32_t s, const f32x4& acc) {
+        const u32x4 av = *reinterpret_cast<const u32x4*>(aRow + s * 32u);
+        const u32x4 bv = *reinterpret_cast<const u32x4*>(bCol + s * 32u);
+        return mfma16<MODE>(av, bv, acc);
+    }
+};
+// fp32 operands converted to fp16 / bf16 in registers (round-to-nearest-even, the same values the convertOperands pass
+// would produce), so the full-matrix conversion pass can be skipped when only a few blocks are dense
+template <int MODE>
+struct FragCvt {
+    typedef float elem;
+    static constexpr uint32_t kLane = 8, kStep = 32;
+    static __device__ __forceinline__ f32x4 step(const elem* aRow, const elem* bCol, uint32_t s, const f32x4& acc) {
+        const f32x4 a0 = *reinterpret_cast<const f32x4*>(aRow + s * 32u);
+        const f32x4 a1 = *reinterpret_cast<const f32x4*>(aRow + s * 32u + 4u);
+        const f32x4 b0 = *reinterpret_cast<const f32x4*>(bCol + s * 32u);
+        const f32x4 b1 = *reinterpret_cast<const f32x4*>(bCol + s * 32u + 4u);
+        return mfma16<MODE>(packLowp<MODE>(a0, a1), packLowp<MODE>(b0, b1), acc);
+    }
+};
+// exact fp32: v_mfma_f32_16x16x4_f32 is a k-ordered fmaf chain.  Lane (r, g) loads float4 chunks [16t + 4g, +4) of its
+// row / column; MFMA number (t, j) multiplies element j of every chunk, so inside it lane group g supplies
+// k = 16t + 4g + j.  Chain order of k: for t, for j, for g.  (CPU twin: oracle_dense_f32_twin.)
+struct FragF32 {
+    typedef float elem;
+    static constexpr uint32_t kLane = 4, kStep = 16;
+    static __device__ __forceinline__ f32x4 step(const elem* aRow, const elem* bCol, uint32_t t, f32x4 acc) {
+        const f32x4 av = *reinterpret_cast<const f32x4*>(aRow + t * 16u);
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(bCol + t * 16u);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc, 0, 0, 0);
+        return acc;
+    }
+};
+
+template <typename F, typename TileT>
+__device__ __forceinline__ void
+denseAnyK(const typename F::elem* A, const typename F::elem* B, uint32_t K, uint32_t H,
+          const uint32_t* groupRows, const uint32_t* groupRowBase,
+          const uint32_t* blockCols, const TileT* tiles,
+          const uint8_t* blockMask, const DenseItem* items,
+          uint32_t numItems, float* P, Batch batch) {
+    A += blockIdx.y * batch.strideA;  // batched call: problem blockIdx.y of a strided batch
+    B += blockIdx.y * batch.strideB;
+    P += blockIdx.y * batch.strideP;
+    const uint32_t itemId = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
+    if (itemId >= numItems) return;
+    const DenseItem item = items[itemId];
+    const uint32_t lane = threadIdx.x & 63u, r = lane & 15u, g = lane >> 4;
+    const uint32_t steps = K / F::kStep;
+    for (uint32_t b = item.first; b < item.first + item.count; ++b) {
+        const uint32_t mask = blockMask[b];
+        const typename F::elem* bCol = B + (size_t)blockCols[(size_t)b * 16u + r] * K + g * F::kLane;
+        for (uint32_t h = 0; h < H; ++h) {
+            if (!(mask & (1u << h))) continue;
+            const uint32_t slot = item.group * 16u * H + h * 16u;
+            const typename F::elem* aRow = A + (size_t)groupRows[slot + r] * K + g * F::kLane;
+            const typename TileLoad<TileT>::raw tile = loadTile<TileT>(tiles, (size_t)b * H + h, lane);
+            uint32_t rowBase[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                rowBase[i] = groupRowBase[(TileLoad<TileT>::windowed ? itemId * 16u * H + h * 16u : slot) + 4u * g + i];
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            for (uint32_t s = 0; s < steps; ++s) acc = F::step(aRow, bCol, s, acc);
+            scatterTile<TileT>(acc, tile, rowBase, P);
+        }
+    }
+}
+
 template <int MODE, typename TileT>
 __global__ void __launch_bounds__(kThreads)
 denseGroupsAnyK(const uint16_t* __restrict__ A16, const uint16_t* __restrict__ B16, uint32_t K, uint32_t H,
@@ -738,43 +822,8 @@ denseGroupsAnyK(const uint16_t* __restrict__ A16, const uint16_t* __restrict__ B
                 const uint32_t* __restrict__ blockCols, const TileT* __restrict__ tiles,
                 const uint8_t* __restrict__ blockMask, const DenseItem* __restrict__ items,
                 uint32_t numItems, float* __restrict__ P, Batch batch) {
-    A16 += blockIdx.y * batch.strideA;  // batched call: problem blockIdx.y of a strided batch
-    B16 += blockIdx.y * batch.strideB;
-    P += blockIdx.y * batch.strideP;
-    const uint32_t itemId = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
-    if (itemId >= numItems) return;
-    const DenseItem item = items[itemId];
-    const uint32_t lane = threadIdx.x & 63u, r = lane & 15u, g = lane >> 4;
-    const uint32_t steps = K >> 5;
-    for (uint32_t b = item.first; b < item.first + item.count; ++b) {
-        const uint32_t mask = blockMask[b];
-        const uint16_t* bCol = B16 + (size_t)blockCols[(size_t)b * 16u + r] * K + g * 8u;
-        for (uint32_t h = 0; h < H; ++h) {
-            if (!(mask & (1u << h))) continue;
-            const uint32_t slot = item.group * 16u * H + h * 16u;
-            const uint16_t* aRow = A16 + (size_t)groupRows[slot + r] * K + g * 8u;
-            const typename TileLoad<TileT>::raw tile = loadTile<TileT>(tiles, (size_t)b * H + h, lane);
-            uint32_t rowBase[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                rowBase[i] = groupRowBase[(TileLoad<TileT>::windowed ? itemId * 16u * H + h * 16u : slot) + 4u * g + i];
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            for (uint32_t s = 0; s < steps; ++s) {
-                const u32x4 av = *reinterpret_cast<const u32x4*>(aRow + s * 32u);
-                const u32x4 bv = *reinterpret_cast<const u32x4*>(bCol + s * 32u);
-                acc = mfma16<MODE>(av, bv, acc);
-            }
-            scatterTile<TileT>(acc, tile, rowBase, P);
-        }
-    }
+    denseAnyK<Frag16<MODE>, TileT>(A16, B16, K, H, groupRows, groupRowBase, blockCols, tiles, blockMask, items, numItems, P, batch);
 }
-
-// ---------------------------------------------------------------------------
-// dense kernel for a SMALL dense part: fp32 operands converted to fp16 / bf16 in
-// registers (round-to-nearest-even, the same values the convertOperands pass
-// would produce), so the full-matrix conversion pass can be skipped when only a
-// few blocks are dense.  One wave per DenseItem, fragments from global memory.
-// ---------------------------------------------------------------------------
 
 template <int MODE, typename TileT>
 __global__ void __launch_bounds__(kThreads)
@@ -783,46 +832,9 @@ denseGroupsCvt(const float* __restrict__ A, const float* __restrict__ B, uint32_
                const uint32_t* __restrict__ blockCols, const TileT* __restrict__ tiles,
                const uint8_t* __restrict__ blockMask, const DenseItem* __restrict__ items,
                uint32_t numItems, float* __restrict__ P, Batch batch) {
-    A += blockIdx.y * batch.strideA;  // batched call: problem blockIdx.y of a strided batch
-    B += blockIdx.y * batch.strideB;
-    P += blockIdx.y * batch.strideP;
-    const uint32_t itemId = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
-    if (itemId >= numItems) return;
-    const DenseItem item = items[itemId];
-    const uint32_t lane = threadIdx.x & 63u, r = lane & 15u, g = lane >> 4;
-    const uint32_t steps = K >> 5;
-    for (uint32_t b = item.first; b < item.first + item.count; ++b) {
-        const uint32_t mask = blockMask[b];
-        const float* bCol = B + (size_t)blockCols[(size_t)b * 16u + r] * K + g * 8u;
-        for (uint32_t h = 0; h < H; ++h) {
-            if (!(mask & (1u << h))) continue;
-            const uint32_t slot = item.group * 16u * H + h * 16u;
-            const float* aRow = A + (size_t)groupRows[slot + r] * K + g * 8u;
-            const typename TileLoad<TileT>::raw tile = loadTile<TileT>(tiles, (size_t)b * H + h, lane);
-            uint32_t rowBase[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                rowBase[i] = groupRowBase[(TileLoad<TileT>::windowed ? itemId * 16u * H + h * 16u : slot) + 4u * g + i];
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            for (uint32_t s = 0; s < steps; ++s) {
-                const f32x4 a0 = *reinterpret_cast<const f32x4*>(aRow + s * 32u);
-                const f32x4 a1 = *reinterpret_cast<const f32x4*>(aRow + s * 32u + 4u);
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(bCol + s * 32u);
-                const f32x4 b1 = *reinterpret_cast<const f32x4*>(bCol + s * 32u + 4u);
-                acc = mfma16<MODE>(packLowp<MODE>(a0, a1), packLowp<MODE>(b0, b1), acc);
-            }
-            scatterTile<TileT>(acc, tile, rowBase, P);
-        }
-    }
+    denseAnyK<FragCvt<MODE>, TileT>(A, B, K, H, groupRows, groupRowBase, blockCols, tiles, blockMask, items, numItems, P, batch);
 }
 
-// ---------------------------------------------------------------------------
-// dense kernel, exact fp32: v_mfma_f32_16x16x4_f32 is a k-ordered fmaf chain.
-// Lane (r, g) loads float4 chunks [16t + 4g, +4) of its row / column; MFMA
-// number (t, j) multiplies element j of every chunk, so inside it lane group g
-// supplies k = 16t + 4g + j.  Chain order of k: for t, for j, for g.
-// (CPU twin: oracle_dense_f32_twin.)  One wave per DenseItem.
-// ---------------------------------------------------------------------------
 template <typename TileT>
 __global__ void __launch_bounds__(kThreads)
 denseGroupsF32(const float* __restrict__ A, const float* __restrict__ B, uint32_t K, uint32_t H,
@@ -830,202 +842,29 @@ denseGroupsF32(const float* __restrict__ A, const float* __restrict__ B, uint32_
                const uint32_t* __restrict__ blockCols, const TileT* __restrict__ tiles,
                const uint8_t* __restrict__ blockMask, const DenseItem* __restrict__ items,
                uint32_t numItems, float* __restrict__ P, Batch batch) {
-    A += blockIdx.y * batch.strideA;  // batched call: problem blockIdx.y of a strided batch
-    B += blockIdx.y * batch.strideB;
-    P += blockIdx.y * batch.strideP;
-    const uint32_t itemId = blockIdx.x * kWavesPerWG + (threadIdx.x >> 6);
-    if (itemId >= numItems) return;
-    const DenseItem item = items[itemId];
-    const uint32_t lane = threadIdx.x & 63u, r = lane & 15u, g = lane >> 4;
-    const uint32_t steps = K >> 4;
-    for (uint32_t b = item.first; b < item.first + item.count; ++b) {
-        const uint32_t mask = blockMask[b];
-        const float* bCol = B + (size_t)blockCols[(size_t)b * 16u + r] * K + g * 4u;
-        for (uint32_t h = 0; h < H; ++h) {
-            if (!(mask & (1u << h))) continue;
-            const uint32_t slot = item.group * 16u * H + h * 16u;
-            const float* aRow = A + (size_t)groupRows[slot + r] * K + g * 4u;
-            const typename TileLoad<TileT>::raw tile = loadTile<TileT>(tiles, (size_t)b * H + h, lane);
-            uint32_t rowBase[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                rowBase[i] = groupRowBase[(TileLoad<TileT>::windowed ? itemId * 16u * H + h * 16u : slot) + 4u * g + i];
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            for (uint32_t t = 0; t < steps; ++t) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(aRow + t * 16u);
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(bCol + t * 16u);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[3], acc, 0, 0, 0);
-            }
-            scatterTile<TileT>(acc, tile, rowBase, P);
-        }
-    }
+    denseAnyK<FragF32, TileT>(A, B, K, H, groupRows, groupRowBase, blockCols, tiles, blockMask, items, numItems, P, batch);
 }
 
 // ---------------------------------------------------------------------------
-// residual sparse kernel (fp32).  One workgroup = one SparseItem.  The panel's
-// 16 A rows are staged in LDS (row stride K+4 floats).  LPE lanes share one
-// entry: lane t accumulates the float4 chunks q = t, t+LPE, ... of the dot
-// product with one fmaf chain (ascending k), then a butterfly over the LPE lanes.
+// Sparse residue.  One workgroup = one SparseItem.  The panel's 16 A rows are staged in LDS (row stride K elements +
+// 16 bytes).  LPE lanes share one entry: lane t accumulates the 16-byte chunks q = t, t+LPE, ... of the dot product in
+// ascending k, four steps per chunk, then a butterfly over the LPE lanes.
+//
+// One body (residueEntries) behind two kernels; an element policy says what a 16-byte chunk holds - elem, chunk (the
+// 16-byte vector), kPerChunk (elements in it) and dot (acc + chunk . chunk, four steps in ascending k):
+//   sparseEntries      fp32 operands (ResidueF32): 4 elements per chunk, one fmaf chain - exact fp32 with a defined
+//                      summation order (bit-level CPU twin: oracle/sddmm_oracle.c oracle_sparse_twin).
+//   sparseEntriesLowp  the fp16 / bf16 operand copies (ResidueLowp<MODE>): 8 elements per chunk through
+//                      v_dot2c_f32_{f16,bf16} (products exact, fp32 accumulation); accuracy class = the dense path's.
+//                      Used when the conversion pass runs anyway (the plan has a dense part): the residue is bound by
+//                      the rate at which B columns can be gathered from L2 (~17-19 TB/s chip-wide on MI355X,
+//                      MI355X_MICROARCH.md "Indexed rows"), so halving the bytes per column is what makes it faster.
 // ---------------------------------------------------------------------------
-constexpr int kSparseLdsPad = 4;  // floats
-
-// CPL > 0: K = 4 * LPE * CPL, every lane's CPL column chunks are requested before the first
-// is used (the residue is a gather: what matters is bytes in flight); CPL = 0: any K.
-// FREE: the residue in global (column, row) order - no panels; `panelRows` then holds one row id per entry
-// and A rows are gathered like B columns (plan_pack.hpp, "Panel form or free form?").
-template <int LPE, bool A_IN_LDS, int CPL = 0, bool FREE = false>
-__global__ void __launch_bounds__(kThreads)
-sparseEntries(const float* __restrict__ A, const float* __restrict__ B, uint32_t K,
-              const uint32_t* __restrict__ panelRows, const uint32_t* __restrict__ entryCol,
-              const uint32_t* __restrict__ entryDst, const uint8_t* __restrict__ entryRow,
-              const SparseItem* __restrict__ items, float* __restrict__ P, Batch batch) {
-    A += blockIdx.y * batch.strideA;  // batched call: problem blockIdx.y of a strided batch
-    B += blockIdx.y * batch.strideB;
-    P += blockIdx.y * batch.strideP;
-    extern __shared__ __attribute__((aligned(16))) float panelA[];
-    const SparseItem item = items[xcdContiguous(blockIdx.x, gridDim.x)];
-    const uint32_t chunks = K >> 2;  // float4 chunks per row
-    const uint32_t ldsStride = K + kSparseLdsPad;
-
-    constexpr uint32_t groups = kThreads / LPE;
-    const uint32_t group = threadIdx.x / LPE;
-    const uint32_t t = threadIdx.x % LPE;
-    // every group runs the same number of rounds so that all lanes of a wave
-    // reach the shuffles together
-    const uint32_t rounds = (item.count + groups - 1) / groups;
-
-    // Tuned shapes over a staged panel: the chain item -> panel rows -> A rows -> barrier -> (entry -> B column)
-    // per round is what a workgroup's time consists of, so the entries of two rounds and the B chunks of the
-    // next round are requested ahead: round 0's before the panel is staged, round r+1's before round r is summed.
-    // Same per-lane arithmetic in the same order as the plain loop below.
-    // (with 8 chunks per lane a second B buffer costs occupancy - Trefethen_20000 K=256 25.4 -> 29.5 us - so those
-    // shapes only keep the entries ahead and request round r+1's chunks right after round r is summed)
-    if constexpr (CPL > 0 && A_IN_LDS && !FREE) {
-        constexpr bool TWO_BUFFERS = CPL <= 4;
-        auto entryOf = [&](uint32_t round, uint32_t& idx, uint32_t& col, uint32_t& row) {
-            const uint32_t e = round * groups + group;
-            idx = item.start + (e < item.count ? e : 0u);
-            col = entryCol[idx];
-            row = entryRow[idx];
-        };
-        auto request = [&](f32x4 (&bv)[CPL], uint32_t col) {
-            const float* bCol = B + (size_t)col * K;
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) bv[c] = *reinterpret_cast<const f32x4*>(bCol + (t + c * LPE) * 4u);
-        };
-        auto finish = [&](const f32x4 (&bv)[CPL], uint32_t round, uint32_t idx, uint32_t row) {
-            const float* aRow = panelA + row * ldsStride;
-            float acc = 0.f;
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(aRow + (t + c * LPE) * 4u);
-                acc = __builtin_fmaf(av[0], bv[c][0], acc);
-                acc = __builtin_fmaf(av[1], bv[c][1], acc);
-                acc = __builtin_fmaf(av[2], bv[c][2], acc);
-                acc = __builtin_fmaf(av[3], bv[c][3], acc);
-            }
-#pragma unroll
-            for (int off = LPE / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, LPE);
-            if (round * groups + group < item.count && t == 0) P[entryDst[idx]] = acc;
-        };
-        uint32_t idx0, col0, row0, idx1, col1, row1;
-        entryOf(0, idx0, col0, row0);
-        entryOf(1, idx1, col1, row1);
-        f32x4 bvA[CPL], bvB[TWO_BUFFERS ? CPL : 1];
-        request(bvA, col0);
-        for (uint32_t i = threadIdx.x; i < 16u * chunks; i += kThreads) {
-            const uint32_t row = i / chunks, q = i - row * chunks;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(
-                A + (size_t)panelRows[item.panel * 16u + row] * K + q * 4u);
-            *reinterpret_cast<f32x4*>(panelA + row * ldsStride + q * 4u) = v;
-        }
-        __syncthreads();
-        if constexpr (TWO_BUFFERS) {
-            for (uint32_t round = 0; round < rounds; round += 2) {
-                uint32_t idx2 = 0, col2 = 0, row2 = 0, idx3 = 0, col3 = 0, row3 = 0;
-                if (round + 1 < rounds) request(bvB, col1);
-                if (round + 2 < rounds) entryOf(round + 2, idx2, col2, row2);
-                finish(bvA, round, idx0, row0);
-                if (round + 1 >= rounds) break;
-                if (round + 2 < rounds) request(bvA, col2);
-                if (round + 3 < rounds) entryOf(round + 3, idx3, col3, row3);
-                finish(bvB, round + 1, idx1, row1);
-                idx0 = idx2; col0 = col2; row0 = row2;
-                idx1 = idx3; col1 = col3; row1 = row3;
-            }
-        } else {
-            for (uint32_t round = 0; round < rounds; ++round) {
-                uint32_t idx2 = 0, col2 = 0, row2 = 0;
-                if (round + 2 < rounds) entryOf(round + 2, idx2, col2, row2);
-                finish(bvA, round, idx0, row0);
-                if (round + 1 < rounds) request(bvA, col1);
-                idx0 = idx1; col0 = col1; row0 = row1;
-                idx1 = idx2; col1 = col2; row1 = row2;
-            }
-        }
-        return;
-    }
-
-    if constexpr (A_IN_LDS) {
-        for (uint32_t i = threadIdx.x; i < 16u * chunks; i += kThreads) {
-            const uint32_t row = i / chunks, q = i - row * chunks;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(
-                A + (size_t)panelRows[item.panel * 16u + row] * K + q * 4u);
-            *reinterpret_cast<f32x4*>(panelA + row * ldsStride + q * 4u) = v;
-        }
-        __syncthreads();
-    }
-    for (uint32_t round = 0; round < rounds; ++round) {
-        const uint32_t e = round * groups + group;
-        const bool live = e < item.count;
-        const uint32_t idx = item.start + (live ? e : 0u);
-        const uint32_t col = entryCol[idx];
-        const uint32_t row = FREE ? panelRows[idx] : (uint32_t)entryRow[idx];
-        const float* bCol = B + (size_t)col * K;
-        const float* aRow = FREE       ? A + (size_t)row * K
-                            : A_IN_LDS ? panelA + row * ldsStride
-                                       : A + (size_t)panelRows[item.panel * 16u + row] * K;
-        float acc = 0.f;
-        if constexpr (CPL > 0) {
-            f32x4 bv[CPL];
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) bv[c] = *reinterpret_cast<const f32x4*>(bCol + (t + c * LPE) * 4u);
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(aRow + (t + c * LPE) * 4u);
-                acc = __builtin_fmaf(av[0], bv[c][0], acc);
-                acc = __builtin_fmaf(av[1], bv[c][1], acc);
-                acc = __builtin_fmaf(av[2], bv[c][2], acc);
-                acc = __builtin_fmaf(av[3], bv[c][3], acc);
-            }
-        } else {
-            for (uint32_t q = t; q < chunks; q += LPE) {
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(bCol + q * 4u);
-                const f32x4 av = *reinterpret_cast<const f32x4*>(aRow + q * 4u);
-                acc = __builtin_fmaf(av[0], bv[0], acc);
-                acc = __builtin_fmaf(av[1], bv[1], acc);
-                acc = __builtin_fmaf(av[2], bv[2], acc);
-                acc = __builtin_fmaf(av[3], bv[3], acc);
-            }
-        }
-#pragma unroll
-        for (int off = LPE / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, LPE);
-        if (live && t == 0) P[entryDst[idx]] = acc;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Sparse residue from the fp16 / bf16 operand copies.  Used when the conversion pass runs
-// anyway (the plan has a dense part): the residue is bound by the rate at which B columns
-// can be gathered from L2 (~17-19 TB/s chip-wide on MI355X, MI355X_MICROARCH.md "Indexed
-// rows"), so halving the bytes per column is what makes it faster.  Same structure as
-// sparseEntries; 16-byte chunks now hold 8 elements and go through v_dot2c_f32_{f16,bf16}
-// (products exact, fp32 accumulation).  Accuracy class = the dense path's.
-// ---------------------------------------------------------------------------
-constexpr uint32_t kSparseLdsPad16 = 16;  // bytes
+// `unit` is what the A rows are addressed in, in LDS and in global memory: elements in fp32, bytes in 16 bits - as the
+// two kernels were written before they shared a body.  Same addresses either way, but the compiler schedules the two
+// spellings differently, and each policy keeps the one under which no instantiation loses a wave of occupancy
+// (sparseEntries<8, true, 4> takes 66 VGPRs with byte offsets, sparseEntriesLowp<8, MODE, true, 8> with element offsets).
+constexpr uint32_t kSparseLdsPad = 16;  // bytes per staged row: a row is K elements + the pad in both policies
 
 template <int MODE>
 __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float acc) {
@@ -1038,25 +877,70 @@ __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float acc) {
     }
 }
 
-// A_FP32 (panel form with LDS staging only): A16 points at the caller's fp32 A and the panel's rows are rounded
+struct ResidueF32 {
+    typedef float elem;
+    typedef f32x4 chunk;
+    typedef float unit;
+    static constexpr uint32_t kPerChunk = 4;
+    static __device__ __forceinline__ float dot(const chunk& a, const chunk& b, float acc) {
+        acc = __builtin_fmaf(a[0], b[0], acc);
+        acc = __builtin_fmaf(a[1], b[1], acc);
+        acc = __builtin_fmaf(a[2], b[2], acc);
+        acc = __builtin_fmaf(a[3], b[3], acc);
+        return acc;
+    }
+};
+template <int MODE>
+struct ResidueLowp {
+    typedef uint16_t elem;
+    typedef u32x4 chunk;
+    typedef uint8_t unit;
+    static constexpr uint32_t kPerChunk = 8;
+    static __device__ __forceinline__ float dot(const chunk& a, const chunk& b, float acc) {
+        acc = dot2<MODE>(a[0], b[0], acc);
+        acc = dot2<MODE>(a[1], b[1], acc);
+        acc = dot2<MODE>(a[2], b[2], acc);
+        acc = dot2<MODE>(a[3], b[3], acc);
+        return acc;
+    }
+    static __device__ __forceinline__ chunk round(const f32x4& lo, const f32x4& hi) { return packLowp<MODE>(lo, hi); }
+};
+
+// CPL > 0: K = kPerChunk * LPE * CPL, every lane's CPL column chunks are requested before the first
+// is used (the residue is a gather: what matters is bytes in flight); CPL = 0: any K.
+// FREE: the residue in global (column, row) order - no panels; `panelRows` then holds one row id per entry
+// and A rows are gathered like B columns (plan_pack.hpp, "Panel form or free form?").
+// A_FP32 (16-bit, panel form with LDS staging only): A points at the caller's fp32 A and the panel's rows are rounded
 // while they are staged - plans without a dense part then convert B alone (half the conversion pass).
-template <int LPE, int MODE, bool A_IN_LDS, int CPL = 0, bool FREE = false, bool A_FP32 = false>
-__global__ void __launch_bounds__(kThreads)
-sparseEntriesLowp(const uint16_t* __restrict__ A16, const uint16_t* __restrict__ B16, uint32_t K,
-                  const uint32_t* __restrict__ panelRows, const uint32_t* __restrict__ entryCol,
-                  const uint32_t* __restrict__ entryDst, const uint8_t* __restrict__ entryRow,
-                  const SparseItem* __restrict__ items, float* __restrict__ P, Batch batch) {
-    A16 += blockIdx.y * batch.strideA * (A_FP32 ? 2u : 1u);  // batched call: problem blockIdx.y of a strided batch
-    B16 += blockIdx.y * batch.strideB;
+template <typename E, int LPE, bool A_IN_LDS, int CPL, bool FREE, bool A_FP32>
+__device__ __forceinline__ void
+residueEntries(const typename E::elem* A, const typename E::elem* B, uint32_t K, const uint32_t* panelRows,
+               const uint32_t* entryCol, const uint32_t* entryDst, const uint8_t* entryRow, const SparseItem* items,
+               float* P, Batch batch) {
+    typedef typename E::elem Elem;
+    typedef typename E::chunk Chunk;
+    typedef typename E::unit Unit;
+    constexpr uint32_t PER = E::kPerChunk, UPC = 16u / (uint32_t)sizeof(Unit);
+    static_assert(sizeof(Chunk) == 16 && PER * sizeof(Elem) == 16, "a chunk is 16 bytes");
+    A += blockIdx.y * batch.strideA * (A_FP32 ? 2u : 1u);  // batched call: problem blockIdx.y of a strided batch
+    B += blockIdx.y * batch.strideB;
     P += blockIdx.y * batch.strideP;
-    extern __shared__ __attribute__((aligned(16))) uint8_t panelA16[];
+    extern __shared__ __attribute__((aligned(16))) uint8_t residueLds[];
+    Unit* panelA = reinterpret_cast<Unit*>(residueLds);
     const SparseItem item = items[xcdContiguous(blockIdx.x, gridDim.x)];
-    const uint32_t chunks = K >> 3;  // 16-byte chunks (8 elements) per row
-    const uint32_t ldsStride = 2u * K + kSparseLdsPad16;
+    const uint32_t chunks = K / PER;  // 16-byte chunks per row
+    const uint32_t ldsStride = ((uint32_t)sizeof(Elem) * K + kSparseLdsPad) / (uint32_t)sizeof(Unit);
     constexpr uint32_t groups = kThreads / LPE;
     const uint32_t group = threadIdx.x / LPE;
     const uint32_t t = threadIdx.x % LPE;
+    // every group runs the same number of rounds so that all lanes of a wave reach the shuffles together
     const uint32_t rounds = (item.count + groups - 1) / groups;
+    // Tuned shapes over a staged panel: the chain item -> panel rows -> A rows -> barrier -> (entry -> B column)
+    // per round is what a workgroup's time consists of, so the entries of two rounds and the B chunks of the
+    // next round are requested ahead: round 0's before the panel is staged, round r+1's before round r is summed.
+    // Same per-lane arithmetic in the same order as the plain loop below.
+    // (with 8 chunks per lane a second B buffer costs occupancy - Trefethen_20000 K=256 25.4 -> 29.5 us - so those
+    // shapes only keep the entries ahead and request round r+1's chunks right after round r is summed)
     constexpr bool PIPELINED = CPL > 0 && A_IN_LDS && !FREE;
     constexpr bool TWO_BUFFERS = CPL <= 4;
     auto entryOf = [&](uint32_t round, uint32_t& idx, uint32_t& col, uint32_t& row) {
@@ -1065,13 +949,13 @@ sparseEntriesLowp(const uint16_t* __restrict__ A16, const uint16_t* __restrict__
         col = entryCol[idx];
         row = entryRow[idx];
     };
-    auto request = [&](u32x4 (&bv)[CPL > 0 ? CPL : 1], uint32_t col) {
-        const uint16_t* bCol = B16 + (size_t)col * K;
+    auto request = [&](Chunk (&bv)[CPL > 0 ? CPL : 1], uint32_t col) {
+        const Elem* bCol = B + (size_t)col * K;
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) bv[c] = *reinterpret_cast<const u32x4*>(bCol + (t + c * LPE) * 8u);
+        for (int c = 0; c < CPL; ++c) bv[c] = *reinterpret_cast<const Chunk*>(bCol + (t + c * LPE) * PER);
     };
     uint32_t idx0 = 0, col0 = 0, row0 = 0, idx1 = 0, col1 = 0, row1 = 0;
-    u32x4 bvA[CPL > 0 ? CPL : 1], bvB[CPL > 0 && TWO_BUFFERS ? CPL : 1];
+    Chunk bvA[CPL > 0 ? CPL : 1], bvB[CPL > 0 && TWO_BUFFERS ? CPL : 1];
     if constexpr (PIPELINED) {  // round 0's entry and B chunks are on their way while the panel is staged
         entryOf(0, idx0, col0, row0);
         entryOf(1, idx1, col1, row1);
@@ -1080,44 +964,29 @@ sparseEntriesLowp(const uint16_t* __restrict__ A16, const uint16_t* __restrict__
 
     if constexpr (A_IN_LDS) {
         static_assert(!A_FP32 || !FREE, "fp32 A is rounded while a panel is staged");
+        static_assert(!A_FP32 || sizeof(Elem) == 2, "only the 16-bit residue rounds A");
         for (uint32_t i = threadIdx.x; i < 16u * chunks; i += kThreads) {
             const uint32_t row = i / chunks, q = i - row * chunks;
-            const size_t at = (size_t)panelRows[item.panel * 16u + row] * K + q * 8u;
+            const size_t at = (size_t)panelRows[item.panel * 16u + row] * K + q * PER;
+            Chunk v;
             if constexpr (A_FP32) {
-                const float* src = reinterpret_cast<const float*>(A16) + at;
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(src);
-                const f32x4 hi = *reinterpret_cast<const f32x4*>(src + 4);
-                if constexpr (MODE == 0) {
-                    f16x8 o;
-                    o[0] = (_Float16)lo[0]; o[1] = (_Float16)lo[1]; o[2] = (_Float16)lo[2]; o[3] = (_Float16)lo[3];
-                    o[4] = (_Float16)hi[0]; o[5] = (_Float16)hi[1]; o[6] = (_Float16)hi[2]; o[7] = (_Float16)hi[3];
-                    *reinterpret_cast<f16x8*>(panelA16 + row * ldsStride + q * 16u) = o;
-                } else {
-                    bf16x8 o;
-                    o[0] = (__bf16)lo[0]; o[1] = (__bf16)lo[1]; o[2] = (__bf16)lo[2]; o[3] = (__bf16)lo[3];
-                    o[4] = (__bf16)hi[0]; o[5] = (__bf16)hi[1]; o[6] = (__bf16)hi[2]; o[7] = (__bf16)hi[3];
-                    *reinterpret_cast<bf16x8*>(panelA16 + row * ldsStride + q * 16u) = o;
-                }
+                const float* src = reinterpret_cast<const float*>(A) + at;
+                v = E::round(*reinterpret_cast<const f32x4*>(src), *reinterpret_cast<const f32x4*>(src + 4));
             } else {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(A16 + at);
-                *reinterpret_cast<u32x4*>(panelA16 + row * ldsStride + q * 16u) = v;
+                v = *reinterpret_cast<const Chunk*>(A + at);
             }
+            *reinterpret_cast<Chunk*>(panelA + row * ldsStride + q * UPC) = v;
         }
         __syncthreads();
     }
 
-    if constexpr (PIPELINED) {  // see sparseEntries: entries two rounds ahead, B chunks one round ahead
-        auto finish = [&](const u32x4 (&bv)[CPL > 0 ? CPL : 1], uint32_t round, uint32_t idx, uint32_t row) {
-            const uint8_t* aRow = panelA16 + row * ldsStride;
+    if constexpr (PIPELINED) {  // entries two rounds ahead, B chunks one round ahead
+        auto finish = [&](const Chunk (&bv)[CPL > 0 ? CPL : 1], uint32_t round, uint32_t idx, uint32_t row) {
+            const Unit* aRow = panelA + row * ldsStride;
             float acc = 0.f;
 #pragma unroll
-            for (int c = 0; c < CPL; ++c) {
-                const u32x4 av = *reinterpret_cast<const u32x4*>(aRow + (t + c * LPE) * 16u);
-                acc = dot2<MODE>(av[0], bv[c][0], acc);
-                acc = dot2<MODE>(av[1], bv[c][1], acc);
-                acc = dot2<MODE>(av[2], bv[c][2], acc);
-                acc = dot2<MODE>(av[3], bv[c][3], acc);
-            }
+            for (int c = 0; c < CPL; ++c)
+                acc = E::dot(*reinterpret_cast<const Chunk*>(aRow + (t + c * LPE) * UPC), bv[c], acc);
 #pragma unroll
             for (int off = LPE / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, LPE);
             if (round * groups + group < item.count && t == 0) P[entryDst[idx]] = acc;
@@ -1154,32 +1023,21 @@ sparseEntriesLowp(const uint16_t* __restrict__ A16, const uint16_t* __restrict__
         const uint32_t idx = item.start + (live ? e : 0u);
         const uint32_t col = entryCol[idx];
         const uint32_t row = FREE ? panelRows[idx] : (uint32_t)entryRow[idx];
-        const uint16_t* bCol = B16 + (size_t)col * K;
-        const uint8_t* aRow =
-            FREE       ? reinterpret_cast<const uint8_t*>(A16 + (size_t)row * K)
-            : A_IN_LDS ? panelA16 + row * ldsStride
-                       : reinterpret_cast<const uint8_t*>(A16 + (size_t)panelRows[item.panel * 16u + row] * K);
+        const Elem* bCol = B + (size_t)col * K;
+        const Unit* aRow =
+            FREE       ? reinterpret_cast<const Unit*>(A + (size_t)row * K)
+            : A_IN_LDS ? panelA + row * ldsStride
+                       : reinterpret_cast<const Unit*>(A + (size_t)panelRows[item.panel * 16u + row] * K);
         float acc = 0.f;
-        if constexpr (CPL > 0) {  // K = 8 * LPE * CPL
-            u32x4 bv[CPL];
+        if constexpr (CPL > 0) {
+            request(bvA, col);
 #pragma unroll
-            for (int c = 0; c < CPL; ++c) bv[c] = *reinterpret_cast<const u32x4*>(bCol + (t + c * LPE) * 8u);
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) {
-                const u32x4 av = *reinterpret_cast<const u32x4*>(aRow + (t + c * LPE) * 16u);
-                acc = dot2<MODE>(av[0], bv[c][0], acc);
-                acc = dot2<MODE>(av[1], bv[c][1], acc);
-                acc = dot2<MODE>(av[2], bv[c][2], acc);
-                acc = dot2<MODE>(av[3], bv[c][3], acc);
-            }
+            for (int c = 0; c < CPL; ++c)
+                acc = E::dot(*reinterpret_cast<const Chunk*>(aRow + (t + c * LPE) * UPC), bvA[c], acc);
         } else {
             for (uint32_t q = t; q < chunks; q += LPE) {
-                const u32x4 bv = *reinterpret_cast<const u32x4*>(bCol + q * 8u);
-                const u32x4 av = *reinterpret_cast<const u32x4*>(aRow + q * 16u);
-                acc = dot2<MODE>(av[0], bv[0], acc);
-                acc = dot2<MODE>(av[1], bv[1], acc);
-                acc = dot2<MODE>(av[2], bv[2], acc);
-                acc = dot2<MODE>(av[3], bv[3], acc);
+                const Chunk bv = *reinterpret_cast<const Chunk*>(bCol + q * PER);
+                acc = E::dot(*reinterpret_cast<const Chunk*>(aRow + q * UPC), bv, acc);
             }
         }
 #pragma unroll
@@ -1187,6 +1045,26 @@ sparseEntriesLowp(const uint16_t* __restrict__ A16, const uint16_t* __restrict__
         if (live && t == 0) P[entryDst[idx]] = acc;
     }
 }
+
+template <int LPE, bool A_IN_LDS, int CPL = 0, bool FREE = false>
+__global__ void __launch_bounds__(kThreads)
+sparseEntries(const float* __restrict__ A, const float* __restrict__ B, uint32_t K,
+              const uint32_t* __restrict__ panelRows, const uint32_t* __restrict__ entryCol,
+              const uint32_t* __restrict__ entryDst, const uint8_t* __restrict__ entryRow,
+              const SparseItem* __restrict__ items, float* __restrict__ P, Batch batch) {
+    residueEntries<ResidueF32, LPE, A_IN_LDS, CPL, FREE, false>(A, B, K, panelRows, entryCol, entryDst, entryRow, items, P, batch);
+}
+
+template <int LPE, int MODE, bool A_IN_LDS, int CPL = 0, bool FREE = false, bool A_FP32 = false>
+__global__ void __launch_bounds__(kThreads)
+sparseEntriesLowp(const uint16_t* __restrict__ A16, const uint16_t* __restrict__ B16, uint32_t K,
+                  const uint32_t* __restrict__ panelRows, const uint32_t* __restrict__ entryCol,
+                  const uint32_t* __restrict__ entryDst, const uint8_t* __restrict__ entryRow,
+                  const SparseItem* __restrict__ items, float* __restrict__ P, Batch batch) {
+    residueEntries<ResidueLowp<MODE>, LPE, A_IN_LDS, CPL, FREE, A_FP32>(A16, B16, K, panelRows, entryCol, entryDst, entryRow, items, P,
+                                                                        batch);
+}
+
 
 // ---------------------------------------------------------------------------
 // batchedMatrixTranspose (reference src/sddmmKernel.cu:2486-2515): out[b][x][y] = in[b][y][x] for

@@ -616,7 +616,7 @@ int streamCheck(const bsmr_rphm_desc* d, const uint32_t* ro, const uint32_t* ci,
     for (size_t b = 0; b < NB; ++b)
         if (!blockSeen[b]) return 19;
     if (dense != pk.numDenseEntries) return 20;
-    // the residue, as sparseEntries / sparseEntriesLowp walk it
+    // the residue, as residueEntries - the one body of sparseEntries and sparseEntriesLowp - walks it
     const uint64_t numSparse = pk.numSparseEntries;
     if (pk.entryCol.size() != numSparse || pk.entryDst.size() != numSparse ||
         (pk.freeResidue ? pk.entryRowId.size() : pk.entryRow.size()) != numSparse)
