@@ -75,7 +75,7 @@ int launchAttnReduce(const bsmr_backward* bw, uint32_t Kv, const float* partial,
     return BSMR_OK;
 }
 
-// t: the element types of V and O as in runGather (O has V's 16-bit format, or t.mode's with fp8 rows; y16 is not read)
+// t: the element types of V and O as in runGather (O has V's 16-bit format, or t.mode's with fp8 / fp4 rows; y16 is not read)
 int runAttention(bsmr_backward* bw, uint32_t Kv, float scale, const float* P, const void* V, void* O, float* m, float* sOut,
                  uint32_t nb, hipStream_t s, const GatherTypes& t = {}) {
     if (int st = growWork(bw, attnWorkFloats(bw, Kv, nb))) return st;
@@ -101,6 +101,15 @@ int runAttention(bsmr_backward* bw, uint32_t Kv, float scale, const float* P, co
                         if (t.scales) launch(bsmr::attnGather8<W(), LANES(), MODE(), FMT(), true>, V8, O16, t.scales, xB / 32u);
                         else launch(bsmr::attnGather8<W(), LANES(), MODE(), FMT()>, V8, O16, kNoScales, (uint64_t)0);
                     });
+                });
+            });
+        } else if (kind == RowKind::FP4) {   // xB elements of a batch are xB / 2 bytes of codes and xB / 32 scale bytes
+            const uint8_t* V4 = static_cast<const uint8_t*>(V);
+            withGatherShape<RowKind::FP4>(g, [&](auto W, auto LANES) {
+                withMode(t.mode, [&](auto MODE) {
+                    hipLaunchKernelGGL((bsmr::attnGather4<W(), LANES(), MODE()>), g.grid, dim3(256), 0, s, bw->items[0],
+                                       bw->numItems[0], g.slices, bw->colIndices, scale, P, m, V4, O16, sOut, partial, sPart, Kv, M,
+                                       slots, nnz, xB / 2u, t.scales, xB / 32u);
                 });
             });
         } else if (kind == RowKind::B16) {

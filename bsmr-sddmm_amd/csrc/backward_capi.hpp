@@ -12,6 +12,7 @@
 
 #include "spmm_blocked_kernels.hpp"   // (includes spmm_kernels.hpp)
 #include "fp8_kernels.hpp"            // the fp8 arms of runGather and runAttention (includes attention_kernels.hpp)
+#include "fp4_kernels.hpp"            // ... and the MXFP4 arms
 
 // Device format of bsmr_backward_attach_blocks (csrc/blocked_capi.hpp).  Residue lists: [0] the rows outside panels with
 // blocks (destination = the row of Y), [1] the rows of panels with blocks (destination = their staging row); the chunk
@@ -174,11 +175,15 @@ struct GatherLists {
 };
 
 // ---- the launch of a gather (spmmGather*, attnGather*): its geometry and its compile-time shape, stated once ----------
-// What the gathered rows are: fp32, fp16 / bf16, or OCP fp8 bytes.
-enum class RowKind { F32, B16, FP8 };
+// What the gathered rows are: fp32, fp16 / bf16, OCP fp8 bytes, or OCP e2m1 nibbles under MX block scales.
+enum class RowKind { F32, B16, FP8, FP4 };
 
 // Source bytes per lane of the fp8 gathers for slice width W (csrc/fp8_kernels.hpp "Lane layout")
 constexpr uint32_t lanes8For(uint32_t W) { return W >= 128u ? 16u : 8u; }
+
+// Source elements per lane of the fp4 gathers for slice width W (csrc/fp4_kernels.hpp "Lane layout"): 16-, 16-, 8- and
+// 4-byte loads
+constexpr uint32_t lanes4For(uint32_t W) { return W >= 128u ? 32u : W == 64u ? 16u : 8u; }
 
 constexpr const uint8_t* kNoScales = nullptr;   // the E of an fp8 gather without MX: never read
 
@@ -191,7 +196,7 @@ auto withFp8(int fmt, F&& fn) {
 struct GatherGeometry {
     uint32_t W;        // slice width: the largest of 256, 128, 64, 32 that divides K
     uint32_t slices;   // per row
-    uint32_t lanes;    // elements (fp8: bytes) a lane loads at once; 0 for fp32 rows, whose kernels have one layout per W
+    uint32_t lanes;    // elements (fp8: bytes, fp4: nibbles) a lane loads at once; 0 for fp32 rows: one layout per W
     uint64_t units;    // items x slices: a unit is one slice of one item
     dim3 grid;
 };
@@ -201,7 +206,10 @@ GatherGeometry gatherGeometry(const bsmr_backward* bw, uint32_t K, uint32_t numI
     g.W = K % 256u == 0 ? 256u : K % 128u == 0 ? 128u : K % 64u == 0 ? 64u : 32u;
     g.slices = K / g.W;
     g.units = (uint64_t)numItems * g.slices;
-    g.lanes = kind == RowKind::F32 ? 0u : kind == RowKind::B16 ? lanes16For(bw, g.W) : lanes8For(g.W);
+    g.lanes = kind == RowKind::F32   ? 0u
+              : kind == RowKind::B16 ? lanes16For(bw, g.W)
+              : kind == RowKind::FP8 ? lanes8For(g.W)
+                                     : lanes4For(g.W);
     // four waves per block; a unit takes W / lanes lanes of a wave - of fp32 rows W / 4, and the whole wave from W = 128 on
     const uint64_t unitsPerBlock =
         kind == RowKind::F32 ? 4u * (g.W >= 128u ? 1u : 64u / (g.W / 4u)) : 4u * (64u / (g.W / g.lanes));
@@ -211,12 +219,14 @@ GatherGeometry gatherGeometry(const bsmr_backward* bw, uint32_t K, uint32_t numI
 
 // fn(W, LANES) with g's slice width and lane layout as compile-time constants.  KIND says which pairs exist, so a caller
 // instantiates its kernel for exactly these: fp32 rows every W (LANES = 0, not a template argument of those kernels);
-// 16-bit rows every W x {4, 8} (BSMR_GATHER16_LANES forces either); fp8 rows (256, 16), (128, 16), (64, 8), (32, 8) alone.
+// 16-bit rows every W x {4, 8} (BSMR_GATHER16_LANES forces either); fp8 rows (256, 16), (128, 16), (64, 8), (32, 8) alone;
+// fp4 rows (256, 32), (128, 32), (64, 16), (32, 8) alone.
 template <RowKind KIND, typename F>
 void withGatherShape(const GatherGeometry& g, F&& fn) {
     auto width = [&](auto W) {
         if constexpr (KIND == RowKind::F32) fn(W, Int<0>{});
         else if constexpr (KIND == RowKind::FP8) fn(W, Int<(int)lanes8For(W())>{});
+        else if constexpr (KIND == RowKind::FP4) fn(W, Int<(int)lanes4For(W())>{});
         else if (g.lanes == 8u) fn(W, Int<8>{});
         else fn(W, Int<4>{});
     };
@@ -231,15 +241,17 @@ void withGatherShape(const GatherGeometry& g, F&& fn) {
 // The element types of a gather.  mode BSMR_COMPUTE_F32: fp32 rows of X into fp32 rows of Y.  Otherwise the rows of X
 // are mode's 16-bit format, and with y16 so are the rows of Y (else fp32).  fp8 >= 0: X holds bytes of that fp8 format
 // instead, widened to mode (y16 is then set); scales non-NULL: each multiplied by its MX block scale ([b][rows][K / 32]).
+// fp4: X holds e2m1 codes, two per byte, under `scales` (y16 is set, fp8 is not read).
 struct GatherTypes {
     int mode = BSMR_COMPUTE_F32;
     bool y16 = false;
     int fp8 = -1;
     const uint8_t* scales = nullptr;
+    bool fp4 = false;
 };
 
 RowKind rowKind(const GatherTypes& t) {
-    return t.fp8 >= 0 ? RowKind::FP8 : t.mode != BSMR_COMPUTE_F32 ? RowKind::B16 : RowKind::F32;
+    return t.fp4 ? RowKind::FP4 : t.fp8 >= 0 ? RowKind::FP8 : t.mode != BSMR_COMPUTE_F32 ? RowKind::B16 : RowKind::F32;
 }
 
 // The gather and the reduction of its split destinations over one set of lists.  vB / xB / yB / pB: the batch strides of
@@ -269,6 +281,18 @@ int runGather(const bsmr_backward* bw, const GatherLists& L, uint32_t K, const f
                             else launch(bsmr::spmmGather8<W(), LANES(), MAP(), MODE(), FMT()>, X8, Y16, kNoScales, (uint64_t)0);
                         });
                     });
+                });
+            });
+        } else if (kind == RowKind::FP4) {   // xB elements of a batch are xB / 2 bytes of codes and xB / 32 scale bytes
+            const uint8_t* X4 = static_cast<const uint8_t*>(Xrows);
+            uint16_t* Y16 = static_cast<uint16_t*>(Yout);
+            auto launch4 = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, g.grid, dim3(256), 0, s, L.items, L.numItems, g.slices, L.src, L.map, v, X4, Y16, partial,
+                                   K, nnz, xB / 2u, yB, pB, t.scales, xB / 32u);
+            };
+            withGatherShape<RowKind::FP4>(g, [&](auto W, auto LANES) {
+                withFlag(map, [&](auto MAP) {
+                    withMode(t.mode, [&](auto MODE) { launch4(bsmr::spmmGather4<W(), LANES(), MAP(), MODE()>); });
                 });
             });
         } else if (kind == RowKind::B16) {

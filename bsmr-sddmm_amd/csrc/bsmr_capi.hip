@@ -3668,3 +3668,4 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
 #include "softmax_capi.hpp"
 #include "attention_capi.hpp"
 #include "fp8_capi.hpp"
+#include "fp4_capi.hpp"

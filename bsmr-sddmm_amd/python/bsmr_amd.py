@@ -268,6 +268,13 @@ HIP_SYMBOLS = {
                                   C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_x8_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
                                     [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_widen_fp4_mx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "bsmr_sddmm_b4_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                   C.c_int, C.c_void_p]),
+    "bsmr_spmm_x4_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_x4_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
+                                    [C.c_uint32, C.c_int, C.c_void_p]),
 }
 
 HOST_SYMBOLS = {
@@ -973,3 +980,34 @@ def sparse_attention_x8_mx(bw, Kv: int, scale: float, P_ptr: int, V8_ptr: int, V
     _check(hip().bsmr_sparse_attention_x8_mx(bw, Kv, scale, P_ptr or None, V8_ptr or None, Vs_ptr or None, O16_ptr or None,
                                              m_ptr or None, s_ptr or None, num_batches, mode, fmt, stream),
            "bsmr_sparse_attention_x8_mx")
+
+
+# --- MXFP4 keys and values: the column-side operand as OCP e2m1 codes, two per byte (element 2i the low nibble of byte
+# i), under E8M0 block scales [b][rows][K/32]; dq = widen(code) * 2^(scale-127) is one exact fp32 multiplication in front
+# of everything else (include/bsmr_hip.h "MXFP4 keys and values").  The scales are mandatory ---
+def widen_fp4_mx(in4_ptr: int, scales_ptr: int, out16_ptr: int, count: int, mode=COMPUTE_F16, stream: int = 0):
+    """out16[i] = narrow(widen(code i) * 2^(scales[i / 32] - 127)); count elements (count / 2 bytes), a multiple of 32"""
+    _check(hip().bsmr_widen_fp4_mx(in4_ptr or None, scales_ptr or None, out16_ptr or None, count, mode, stream),
+           "bsmr_widen_fp4_mx")
+
+
+def sddmm_b4_mx(plan, K: int, A16_ptr: int, B4_ptr: int, Bs_ptr: int, P_ptr: int, num_batches: int = 1, mode=COMPUTE_F16,
+                stream: int = 0):
+    """sddmm_16(A16, narrow(dq(B4, Bs))): B is dequantised into the plan's 16-bit workspace, A16 is read in place"""
+    _check(hip().bsmr_sddmm_b4_mx(plan, K, A16_ptr or None, B4_ptr or None, Bs_ptr or None, P_ptr or None, num_batches,
+                                  mode, stream), "bsmr_sddmm_b4_mx")
+
+
+def spmm_x4_mx(bw, K: int, transpose: bool, v_ptr: int, X4_ptr: int, Xs_ptr: int, Y16_ptr: int, num_batches: int = 1,
+               stream: int = 0, mode=COMPUTE_F16):
+    """Y16 = round(S_v dq(X4, Xs)) (transpose True: S_v^T): the fp32 gather on the dequantised rows, no copy"""
+    _check(hip().bsmr_spmm_x4_mx(bw, K, int(bool(transpose)), v_ptr or None, X4_ptr or None, Xs_ptr or None, Y16_ptr,
+                                 num_batches, mode, stream), "bsmr_spmm_x4_mx")
+
+
+def sparse_attention_x4_mx(bw, Kv: int, scale: float, P_ptr: int, V4_ptr: int, Vs_ptr: int, O16_ptr: int, m_ptr: int,
+                           s_ptr: int, num_batches: int = 1, stream: int = 0, mode=COMPUTE_F16):
+    """sparse_attention on dq(V4, Vs): O16 rounded once (mode's format), m and s those of the fp32 call"""
+    _check(hip().bsmr_sparse_attention_x4_mx(bw, Kv, scale, P_ptr or None, V4_ptr or None, Vs_ptr or None, O16_ptr or None,
+                                             m_ptr or None, s_ptr or None, num_batches, mode, stream),
+           "bsmr_sparse_attention_x4_mx")

@@ -84,6 +84,26 @@ raises ValueError.  bf16 is the format to put beside an MXFP8 Kt: the 16-bit cop
 bf16 for every scale code >= 3 (e4m3) / >= 10 (e5m2), in fp16 only for shifts in [-15, 7] / [-8, 0].
 mx_quantize / mx_dequantize (plain torch, not a hot path) make and read such tensors.
 
+MXFP4 keys and values.  B / Kt, X and V may also be torch.float4_e2m1fn_x2 (where torch has the dtype): OCP e2m1 codes, two
+per byte, element 2i the low nibble of byte i; shape (rows, K/2) or (b, rows, K/2) with K = 2 * shape[-1] a positive multiple
+of 32 (include/bsmr_hip.h "MXFP4 keys and values").  The matching scale keyword is then required (ValueError without it):
+the same E8M0 tensor as above, (rows, K/32) or (b, rows, K/32).  dq = widen(code) * scale is exact in fp32 for every scale
+code up to 254, and the calls are bsmr_sddmm_b4_mx, bsmr_spmm_x4_mx and bsmr_sparse_attention_x4_mx, forward and backward,
+through autograd functions of their own in front of the dispatch above (a call without an fp4 tensor runs the code it ran
+before):
+    sddmm(A, B4, B_scale=Bs):  dA = bsmr_spmm_x4_mx(dP, B4, Bs)
+    spmm(values, X4, out_dtype=..., X_scale=Xs):  d values = bsmr_sddmm_b4_mx(dY, X4, Xs);  transpose=True is refused
+    softmax_spmm(values, X4, scale, out_dtype=..., X_scale=Xs):  dW = bsmr_sddmm_b4_mx(dO, X4, Xs), then
+                   bsmr_sparse_attention_backward_16 on (O, dO)
+    attention(Q, Kt, V):  Kt and V independently fp4, fp8 or 16-bit; out_dtype as for fp8
+No gradient goes into codes or scales (ValueError if either requires grad); a blocked=True operator sends an fp4 X to the
+gather.  Each call equals, bit for bit, the MXFP8 call on the e4m3 re-encoding of the codes with the same scales.  The
+16-bit copy sddmm dequantises into is exact in bf16 for all 256 scale codes, in fp16 only for shifts in [-23, 13]: put
+bf16 beside an MXFP4 Kt.  mx_quantize(x, torch.float4_e2m1fn_x2) / mx_dequantize work on the uint8 view (torch has no CPU
+cast for the dtype): round to nearest, ties to the even code, saturating at +-6; NaN has no code (ValueError).
+Out of scope: MXFP6, NVFP4 (fp8 scales per 16 elements), fp4 on the scaled MFMA of the dense engine, fp4 outputs or
+row-side operands, any change to defaults or the tuner.
+
 Every call runs on torch.cuda.current_stream(device).  Operands are contiguous, on the operator's device, with
 K a positive multiple of 32; anything else raises ValueError.  Double backward is not supported.  Calls on one operator
 share its workspaces: issue them from one thread (the current stream orders them).
@@ -103,10 +123,29 @@ _MODE8 = {torch.float8_e4m3fn: eng.FP8_E4M3, torch.float8_e5m2: eng.FP8_E5M2}
 _EMAX8 = {torch.float8_e4m3fn: 8, torch.float8_e5m2: 15}   # exponent of the largest normal: 448 = 1.75 2^8, 57344 = 1.75 2^15
 _SCALE_DTYPES = (torch.uint8,) + ((torch.float8_e8m0fnu,) if hasattr(torch, "float8_e8m0fnu") else ())
 MX_BLOCK = 32
+_FP4 = getattr(torch, "float4_e2m1fn_x2", None)   # two e2m1 codes per byte, element 2i in the low nibble
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # the magnitude of code 0 .. 7; bit 3 is the sign
+_E2M1_TIES = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)   # the midpoint between codes i and i + 1
 
 
 def _is8(t) -> bool:
     return isinstance(t, torch.Tensor) and t.dtype in _MODE8
+
+
+def _is4(t) -> bool:
+    return _FP4 is not None and isinstance(t, torch.Tensor) and t.dtype == _FP4
+
+
+def _k_of(t: torch.Tensor) -> int:
+    """elements per row of a column-side operand: an fp4 tensor packs two per byte"""
+    return 2 * t.shape[-1] if _is4(t) else t.shape[-1]
+
+
+def _widen4(codes: torch.Tensor) -> torch.Tensor:
+    """(..., K/2) packed e2m1 -> (..., K) fp32 by the table, low nibble first; -0 keeps its sign"""
+    b = codes.view(torch.uint8).to(torch.int64)
+    table = torch.tensor(_E2M1 + tuple(-x for x in _E2M1), dtype=torch.float32, device=codes.device)
+    return torch.stack((table[b & 15], table[b >> 4]), dim=-1).reshape(tuple(codes.shape[:-1]) + (2 * codes.shape[-1],))
 
 
 def _mx_scale_f32(scales: torch.Tensor) -> torch.Tensor:
@@ -121,13 +160,14 @@ def _mx_scale_f32(scales: torch.Tensor) -> torch.Tensor:
 def mx_dequantize(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     """widen(codes) * 2^(scales - 127) per block of 32 along the last dimension, one fp32 multiplication per element (the
     dq of include/bsmr_hip.h "MX block scales"), then cast to dtype.  codes (..., K) fp8, scales (..., K/32)."""
-    if not _is8(codes):
-        raise ValueError(f"codes: dtype {getattr(codes, 'dtype', None)}, expected torch.float8_e4m3fn or torch.float8_e5m2")
-    K = codes.shape[-1]
+    if not (_is8(codes) or _is4(codes)):
+        raise ValueError(f"codes: dtype {getattr(codes, 'dtype', None)}, expected torch.float8_e4m3fn, torch.float8_e5m2 or "
+                         "torch.float4_e2m1fn_x2")
+    K = _k_of(codes)   # fp4: (..., K/2) bytes
     if K % MX_BLOCK or tuple(scales.shape) != tuple(codes.shape[:-1]) + (K // MX_BLOCK,):
         raise ValueError(f"scales: shape {tuple(scales.shape)} beside codes {tuple(codes.shape)}, expected one per 32 elements")
     sc = _mx_scale_f32(scales).repeat_interleave(MX_BLOCK, dim=-1)
-    return (codes.to(torch.float32) * sc).to(dtype)
+    return ((_widen4(codes) if _is4(codes) else codes.to(torch.float32)) * sc).to(dtype)
 
 
 def mx_quantize(x: torch.Tensor, fp8_dtype=torch.float8_e4m3fn):
@@ -136,9 +176,14 @@ def mx_quantize(x: torch.Tensor, fp8_dtype=torch.float8_e4m3fn):
     block gets 0), then x / 2^(e-127) cast with round to nearest even, saturating at the format's largest finite value
     (+-inf saturate too, NaN stays NaN).  codes in fp8_dtype, scales torch.uint8 (..., K/32).  A finite x never dequantises
     to a non-finite value.  A block whose amax has a mantissa above 1.75 saturates its largest e4m3 elements (the known
-    clipping of the floor rule); e5m2 mantissas end at 1.75."""
+    clipping of the floor rule); e5m2 mantissas end at 1.75.
+    fp8_dtype torch.float4_e2m1fn_x2: MXFP4, emax_elem = 2 (6 = 1.5 2^2); codes (..., K/2) packed low nibble first, rounded
+    to nearest with ties to the even code, saturating at +-6 (a block whose amax has a mantissa above 1.5 saturates or
+    rounds its largest elements to 6); NaN has no e2m1 code and raises ValueError."""
+    if _FP4 is not None and fp8_dtype == _FP4:
+        return _mx_quantize4(x)
     if fp8_dtype not in _MODE8:
-        raise ValueError(f"fp8_dtype: {fp8_dtype!r}, expected torch.float8_e4m3fn or torch.float8_e5m2")
+        raise ValueError(f"fp8_dtype: {fp8_dtype!r}, expected torch.float8_e4m3fn, torch.float8_e5m2 or torch.float4_e2m1fn_x2")
     K = x.shape[-1]
     if K == 0 or K % MX_BLOCK:
         raise ValueError(f"x: K = {K}, expected a positive multiple of 32")
@@ -152,6 +197,28 @@ def mx_quantize(x: torch.Tensor, fp8_dtype=torch.float8_e4m3fn):
     top = float(torch.finfo(fp8_dtype).max)
     codes = scaled.clamp(-top, top).to(torch.float32).to(fp8_dtype).reshape(x.shape)   # clamp keeps NaN
     return codes, e.to(torch.uint8)
+
+
+def _mx_quantize4(x: torch.Tensor):
+    K = x.shape[-1]
+    if K == 0 or K % MX_BLOCK:
+        raise ValueError(f"x: K = {K}, expected a positive multiple of 32")
+    if torch.isnan(x).any():
+        raise ValueError("x: NaN has no e2m1 code")
+    blocks = x.to(torch.float64).reshape(tuple(x.shape[:-1]) + (K // MX_BLOCK, MX_BLOCK))
+    mag = blocks.abs()
+    amax = torch.where(torch.isfinite(mag), mag, torch.zeros_like(mag)).amax(dim=-1)
+    _, exp = torch.frexp(amax)                       # floor(log2 amax) = exp - 1
+    e = (exp.to(torch.int64) - 1 - 2 + 127).clamp(0, 254)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    a = mag * torch.exp2((127 - e).to(torch.float64)).unsqueeze(-1)   # exact: a power of two in fp64
+    code = torch.zeros_like(a, dtype=torch.int64)
+    for i, mid in enumerate(_E2M1_TIES):             # nearest; a tie goes up only to an even code; beyond 5: code 7 = 6
+        code += (a > mid) | ((a == mid) & bool((i + 1) % 2 == 0))
+    code |= torch.signbit(blocks).to(torch.int64) << 3
+    code = code.reshape(tuple(x.shape[:-1]) + (K // 2, 2))
+    packed = (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8)    # element 2i in the low nibble
+    return packed.view(_FP4), e.to(torch.uint8)
 
 
 class SparseOperator:
@@ -194,6 +261,9 @@ class SparseOperator:
     def sddmm(self, A: torch.Tensor, B: torch.Tensor, B_scale=None) -> torch.Tensor:
         """P = (A B^T) at S's stored positions: A (M,K) / B (N,K), or (b,M,K) / (b,N,K); P (nnz,) or (b,nnz).
         B may be fp8 (e4m3fn / e5m2) beside an fp16 / bf16 A: no gradient reaches it.  B_scale: its MX block scales."""
+        if _is4(B):
+            self._no_grad8(B, "B")
+            return _SDDMM4.apply(self, A, B, self._check_scale(B_scale, "B_scale", B))
         if _is8(B):
             self._no_grad8(B, "B")
             return _SDDMM8.apply(self, A, B, None if B_scale is None else self._check_scale(B_scale, "B_scale", B))
@@ -206,6 +276,9 @@ class SparseOperator:
         leading b on values (b,nnz) and X.  fp8 X: out_dtype (torch.float16 or torch.bfloat16) is Y's dtype and
         transpose must be False; on a blocked=True operator it takes the gather (the blocked SpMM has no fp8 form).
         X_scale: the MX block scales of an fp8 X."""
+        if _is4(X):
+            self._fp4_call(X, transpose, out_dtype)
+            return _SpMM4.apply(self, values, X, out_dtype, self._check_scale(X_scale, "X_scale", X))
         if self._fp8_call(X, transpose, out_dtype):
             return _SpMM8.apply(self, values, X, out_dtype,
                                 None if X_scale is None else self._check_scale(X_scale, "X_scale", X))
@@ -222,6 +295,9 @@ class SparseOperator:
         """spmm(softmax(values, scale), X) in one gather (bsmr_sparse_attention): values (nnz,) or (b, nnz) fp32, X (N, K)
         or (b, N, K) in fp32, fp16 or bf16 -> Y (M, K) in X's dtype.  A row of S without entries, or whose entries are
         all -inf, gives a zero row; a NaN or +inf makes its row NaN.  fp8 X: Y in out_dtype and X_scale, the rules of spmm."""
+        if _is4(X):
+            self._fp4_call(X, False, out_dtype)
+            return _SoftmaxSpMM4.apply(self, values, X, scale, out_dtype, self._check_scale(X_scale, "X_scale", X))
         if self._fp8_call(X, False, out_dtype):
             return _SoftmaxSpMM8.apply(self, values, X, scale, out_dtype,
                                        None if X_scale is None else self._check_scale(X_scale, "X_scale", X))
@@ -233,14 +309,16 @@ class SparseOperator:
         """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
         positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row.
         fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order.
-        Kt and V may each be fp8; out_dtype (default Q.dtype) is the result's dtype when V is fp8, unused otherwise.
+        Kt and V may each be fp8 or fp4; out_dtype (default Q.dtype) is the result's dtype when V is, unused otherwise.
         Kt_scale / V_scale: the MX block scales of an fp8 Kt / V, independently of each other."""
-        self._no_scale(None if _is8(Kt) else Kt_scale, "Kt_scale", "Kt")   # both refused before any device work
-        self._no_scale(None if _is8(V) else V_scale, "V_scale", "V")
+        self._no_scale(None if _is8(Kt) or _is4(Kt) else Kt_scale, "Kt_scale", "Kt")   # both refused before any device work
+        self._no_scale(None if _is8(V) or _is4(V) else V_scale, "V_scale", "V")
+        if _is4(V):
+            self._check_scale(V_scale, "V_scale", V)   # mandatory: refused here, not behind the SDDMM
         P = self.sddmm(Q, Kt, B_scale=Kt_scale)
         if scale is None:
             scale = Q.shape[-1] ** -0.5
-        out_dtype = (Q.dtype if out_dtype is None else out_dtype) if _is8(V) else None
+        out_dtype = (Q.dtype if out_dtype is None else out_dtype) if _is8(V) or _is4(V) else None
         if fused:
             return self.softmax_spmm(P, V, scale, out_dtype=out_dtype, X_scale=V_scale)
         return self.spmm(self.softmax(P, scale), V, out_dtype=out_dtype, X_scale=V_scale)
@@ -263,7 +341,9 @@ class SparseOperator:
             raise ValueError(f"{name}: MX block scales belong to an fp8 {operand}, this one is not fp8")
 
     def _check_scale(self, sc, name: str, t8: torch.Tensor) -> torch.Tensor:
-        """the MX block scales of the fp8 operand t8 as a uint8 tensor; t8 itself is checked by the call"""
+        """the MX block scales of the fp8 or fp4 operand t8 as a uint8 tensor; t8 itself is checked by the call"""
+        if sc is None:
+            raise ValueError(f"{name}: missing - an fp4 operand always carries MX block scales")
         if not isinstance(sc, torch.Tensor):
             raise ValueError(f"{name}: expected a torch.Tensor")
         if sc.dtype not in _SCALE_DTYPES:
@@ -272,7 +352,7 @@ class SparseOperator:
             raise ValueError(f"{name}: a scale tensor that requires grad - no gradient is computed into scales")
         if sc.device != self.device:
             raise ValueError(f"{name}: on {sc.device}, the operator lives on {self.device}")
-        want = tuple(t8.shape[:-1]) + (t8.shape[-1] // MX_BLOCK,) if isinstance(t8, torch.Tensor) and t8.dim() in (2, 3) else None
+        want = tuple(t8.shape[:-1]) + (_k_of(t8) // MX_BLOCK,) if isinstance(t8, torch.Tensor) and t8.dim() in (2, 3) else None
         if want is None or tuple(sc.shape) != want:
             raise ValueError(f"{name}: shape {tuple(sc.shape)}, expected {want}: the operand's batch and rows, K/32 blocks")
         if not sc.is_contiguous():
@@ -291,6 +371,36 @@ class SparseOperator:
             raise ValueError("transpose=True with an fp8 X: the row-side operand is never fp8")
         self._no_grad8(X, "X")
         return True
+
+    def _fp4_call(self, X, transpose, out_dtype):
+        """the rules of _fp8_call for an fp4 X"""
+        if out_dtype not in _MODE16:
+            raise ValueError(f"out_dtype: {out_dtype!r}, an fp4 X needs torch.float16 or torch.bfloat16")
+        if transpose:
+            raise ValueError("transpose=True with an fp4 X: the row-side operand is never fp4")
+        self._no_grad8(X, "X")
+
+    def _check4(self, t: torch.Tensor, name: str, rows: int, batch):
+        """_check for an fp4 tensor (rows, K/2) or (b, rows, K/2): returns (b or None, K) with K in elements"""
+        if not _is4(t):
+            raise ValueError(f"{name}: dtype {getattr(t, 'dtype', None)}, expected torch.float4_e2m1fn_x2")
+        if t.device != self.device:
+            raise ValueError(f"{name}: on {t.device}, the operator lives on {self.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: not contiguous")
+        if t.dim() not in (2, 3) or t.shape[-2] != rows:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, expected ({rows}, K/2) or (b, {rows}, K/2)")
+        b = t.shape[0] if t.dim() == 3 else None
+        if batch is not None and b != batch[0]:
+            raise ValueError(f"{name}: shape {tuple(t.shape)} does not match the batch of the other operand")
+        K = 2 * t.shape[-1]
+        if K == 0 or K % 32:
+            raise ValueError(f"{name}: K = {K} ({t.shape[-1]} bytes per row), expected a positive multiple of 32")
+        if b == 0:
+            raise ValueError(f"{name}: empty batch")
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name}: data not 16-byte aligned")
+        return b, K
 
     def _check(self, t: torch.Tensor, name: str, rows: int, batch, fp8: bool = False):
         """batch None: either (rows, K) or (b, rows, K); returns (b or None, K).  fp8: the tensor must be fp8"""
@@ -417,6 +527,41 @@ class SparseOperator:
                                 b or 1, self._stream(), mode=_MODE16[out_dtype], fmt=_MODE8[X8.dtype])
         return O, m, s
 
+    # --- MXFP4 column-side operand: the calls above on e2m1 codes, the scales mandatory ---
+    def _sddmm_b4(self, A: torch.Tensor, B4: torch.Tensor, Bs: torch.Tensor) -> torch.Tensor:
+        b, K = self._check(A, "A", self.M, None)
+        _, K2 = self._check4(B4, "B", self.N, (b,))
+        if A.dtype not in _MODE16:
+            raise ValueError(f"A: dtype {A.dtype} beside an fp4 B, expected torch.float16 or torch.bfloat16")
+        if K2 != K:
+            raise ValueError(f"A and B disagree on K ({K} vs {K2})")
+        P = torch.empty((self.nnz,) if b is None else (b, self.nnz), dtype=torch.float32, device=self.device)
+        if self.nnz:
+            eng.sddmm_b4_mx(self._plan, K, A.data_ptr(), B4.data_ptr(), Bs.data_ptr(), P.data_ptr(), b or 1, _MODE16[A.dtype],
+                            self._stream())
+        return P
+
+    def _spmm_x4(self, v: torch.Tensor, X4: torch.Tensor, out_dtype, Xs: torch.Tensor) -> torch.Tensor:
+        """Y (M, K) in out_dtype; the gather also on a blocked operator"""
+        b, K = self._check4(X4, "X", self.N, None)
+        self._check_values(v, b)
+        Y = torch.empty((self.M, K) if b is None else (b, self.M, K), dtype=out_dtype, device=self.device)
+        eng.spmm_x4_mx(self._bw, K, False, v.data_ptr(), X4.data_ptr(), Xs.data_ptr(), Y.data_ptr(), b or 1, self._stream(),
+                       mode=_MODE16[out_dtype])
+        return Y
+
+    def _attention_x4(self, v: torch.Tensor, X4: torch.Tensor, scale, out_dtype, Xs: torch.Tensor):
+        """_attention on fp4 rows: O in out_dtype"""
+        b, K = self._check4(X4, "X", self.N, None)
+        _, scale = self._softmax_args(v, scale)
+        self._check_values(v, b)
+        O = torch.empty((self.M, K) if b is None else (b, self.M, K), dtype=out_dtype, device=self.device)
+        m = torch.empty((self.M,) if b is None else (b, self.M), dtype=torch.float32, device=self.device)
+        s = torch.empty_like(m)
+        eng.sparse_attention_x4_mx(self._bw, K, scale, v.data_ptr(), X4.data_ptr(), Xs.data_ptr(), O.data_ptr(), m.data_ptr(),
+                                   s.data_ptr(), b or 1, self._stream(), mode=_MODE16[out_dtype])
+        return O, m, s
+
     def _softmax_args(self, v: torch.Tensor, scale):
         if not isinstance(v, torch.Tensor):
             raise ValueError("values: expected a torch.Tensor")
@@ -538,6 +683,61 @@ class _SDDMM8(torch.autograd.Function):
         if not ctx.needs_input_grad[1]:
             return None, None, None, None
         return None, ctx.op._spmm_x8(_grad(dP), B8, A.dtype, ctx.Bs), None, None
+
+
+class _SDDMM4(torch.autograd.Function):
+    """sddmm with an fp4 B under the block scales Bs: dA = S_dP dq(B4, Bs) in A's dtype, nothing into B or Bs"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, A, B4, Bs):
+        ctx.op, ctx.Bs = op, Bs
+        ctx.save_for_backward(A, B4)
+        return op._sddmm_b4(A, B4, Bs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dP):
+        A, B4 = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        return None, ctx.op._spmm_x4(_grad(dP), B4, A.dtype, ctx.Bs), None, None
+
+
+class _SpMM4(torch.autograd.Function):
+    """spmm with an fp4 X under the block scales Xs: d values = sddmm(dY, dq(X4, Xs)), nothing into X or Xs"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, values, X4, out_dtype, Xs):
+        ctx.op, ctx.out_dtype, ctx.Xs = op, out_dtype, Xs
+        ctx.save_for_backward(X4)
+        return op._spmm_x4(values, X4, out_dtype, Xs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dY):
+        (X4,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        return None, ctx.op._sddmm_b4(_grad(dY, ctx.out_dtype), X4, ctx.Xs), None, None, None
+
+
+class _SoftmaxSpMM4(torch.autograd.Function):
+    """softmax_spmm with an fp4 X under the block scales Xs: the backward of _SoftmaxSpMM without dX"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, values, X4, scale, out_dtype, Xs):
+        O, m, s = op._attention_x4(values, X4, scale, out_dtype, Xs)
+        ctx.op, ctx.scale, ctx.Xs = op, float(scale), Xs
+        ctx.save_for_backward(values, X4, m, s, O)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        op = ctx.op
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None
+        values, X4, m, s, O = ctx.saved_tensors
+        dO = _grad(dO, O.dtype)
+        dP, _ = op._attention_backward(values, m, s, op._sddmm_b4(dO, X4, ctx.Xs), O, dO, ctx.scale)
+        return None, dP, None, None, None, None
 
 
 class _SpMM8(torch.autograd.Function):

@@ -823,7 +823,56 @@ int bsmr_sparse_attention_x8_mx(bsmr_backward *bw, uint32_t Kv, float scale, con
                                 const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev, uint32_t num_batches,
                                 int compute_mode, int fp8_format, void *stream);
 
-/* ---- Blocked SpMM: Y = S_v X over the RPHM's dense 16 x 16 blocks (revision 5, added without any layout change) ----
+/* ---- MXFP4 keys and values (revision 5, added without any layout change; no reference counterpart) ----
+ * The column-side operand of the four calls above in the smallest OCP Microscaling format, as an MXFP4 KV cache holds it.
+ *   Element  OCP e2m1, 4 bits: bit 3 the sign, bits 2:0 the magnitude code; codes 0 .. 7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6.
+ *            No infinity, no NaN; code 8 is -0 and keeps its sign.
+ *   Packing  element 2i of a row is the low nibble (bits 3:0) of byte i, element 2i + 1 the high nibble - the layout of
+ *            torch.float4_e2m1fn_x2.  A row of K elements is K / 2 bytes (K a positive multiple of 32: a multiple of 16
+ *            bytes), the batch stride rows * K / 2 bytes; the array is 16-byte aligned.
+ *   Scales   exactly those of "MX block scales": uint8 [b][rows][K / 32], one E8M0 code per 32 consecutive elements (16
+ *            bytes), contiguous, read by byte loads at any alignment; code e is 2^(e - 127), e = 0 the fp32 subnormal
+ *            2^-127, e = 255 NaN.  They are mandatory: there is no unscaled fp4 call; scale code 127 gives the plain values.
+ *
+ * Numerical contract.  dq(X4, E)[r][k] = widen(code[r][k]) * 2^(E[r][k / 32] - 127): one IEEE fp32 multiplication of the
+ * exactly widened code, made before the element enters the fma chain (the scale is not folded into the weight).  The
+ * product is exact for every scale code 0 .. 254 (subnormal results are kept: 0.5 * 2^-127 = 2^-128), finite for every
+ * code up to scale code 252; from 253 on the large magnitudes overflow to +-inf; scale code 255 makes every element NaN,
+ * the zeros included.  With narrow = the cast of the 16-bit forms:
+ *   bsmr_widen_fp4_mx(in4, scales, out16, count)   out16[i] = narrow(dq(in4, scales)[i]); count elements, a multiple of 32
+ *                                                  (in4 holds count / 2 bytes)
+ *   bsmr_sddmm_b4_mx(A16, B4, Bs)               == bsmr_sddmm_16(A16, narrow(dq(B4, Bs)))
+ *   bsmr_spmm_x4_mx(v, X4, Xs)                  == narrow(bsmr_spmm(v, dq(X4, Xs))), each output rounded once; both directions
+ *   bsmr_sparse_attention_x4_mx(P, V4, Vs)      == bsmr_sparse_attention(P, dq(V4, Vs)) with O rounded once; m and s are
+ *                                                  bit for bit those of the fp32 call
+ * Every e2m1 value is an e4m3 value, so each call also equals, bit for bit, its _x8_mx / _b8_mx form (BSMR_FP8_E4M3) on
+ * the re-encoded codes with the same scales.  The narrowing in bsmr_sddmm_b4_mx is exact with BSMR_COMPUTE_BF16 for all
+ * 256 scale codes (a bf16 has fp32's exponent range and e2m1 needs two significand bits); with BSMR_COMPUTE_F16 it is
+ * exact only for shifts e - 127 in [-23, 13] (scale codes 104 .. 140) - below, 0.5 and 1.5 fall under fp16's smallest
+ * subnormal step, above, 6 * 2^14 overflows.  Use bf16 beside an MXFP4 Kt.
+ *
+ * compute_mode is BSMR_COMPUTE_F16 or BSMR_COMPUTE_BF16.  Checked before any device work, in the order of the fp8 forms:
+ * a NULL plan / handle or a non-finite scale (BSMR_ERR_INVALID_ARG), K = 0 or not a multiple of 32
+ * (BSMR_ERR_UNSUPPORTED_K), compute_mode, then the pointers - 16 bytes for the fp4 and the 16-bit arrays, 4 for P, v, m
+ * and s; the scales NULL only where nothing is read (nnz = 0; count = 0), at any alignment - and more than 65535 batches.
+ * num_batches = 0 is a no-op behind them.  bsmr_widen_fp4_mx: a count that is not a multiple of 32 is
+ * BSMR_ERR_INVALID_ARG, count = 0 a no-op whatever the pointers.  bsmr_sddmm_b4_mx dequantises into the plan's 16-bit
+ * workspace as bsmr_sddmm_b8_mx does; the two gathers read K / 2 bytes per source row (row and batch offsets formed in
+ * 64 bits) and one scale byte per source row and lane, and make no copy.  Workspaces (bsmr_backward_reserve /
+ * bsmr_sparse_attention_reserve), lists, chunks and reproducibility are those of the 16-bit calls.
+ * Out of scope: MXFP6, fp8 scales per 16 elements (NVFP4), fp4 on the scaled MFMA of the dense engine, fp4 outputs or
+ * row-side operands. */
+int bsmr_widen_fp4_mx(const void *in4_dev, const void *scales_dev, void *out16_dev, uint64_t count, int compute_mode,
+                      void *stream);
+int bsmr_sddmm_b4_mx(bsmr_plan *plan, uint32_t K, const void *A16_dev, const void *B4_dev, const void *B_scales_dev,
+                     float *P_dev, uint32_t num_batches, int compute_mode, void *stream);
+int bsmr_spmm_x4_mx(bsmr_backward *bw, uint32_t K, int transpose, const float *v_dev, const void *X4_dev,
+                    const void *X_scales_dev, void *Y16_dev, uint32_t num_batches, int compute_mode, void *stream);
+int bsmr_sparse_attention_x4_mx(bsmr_backward *bw, uint32_t Kv, float scale, const float *P_dev, const void *V4_dev,
+                                const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev, uint32_t num_batches,
+                                int compute_mode, void *stream);
+
+/* ---- Blocked SpMM:Y = S_v X over the RPHM's dense 16 x 16 blocks (revision 5, added without any layout change) ----
  * The row direction of bsmr_spmm with the dense part of the reordering put to use: in a row panel the 16 columns of a
  * dense block are shared by 16 output rows, so a row of X is read once per block instead of once per stored entry and the
  * block is multiplied on v_mfma_f32_16x16x4_f32.  Opt-in: a handle serves these calls after
