@@ -1489,7 +1489,8 @@ int ensureGemm(bsmr_plan* p, uint32_t K) {
     }
 }
 
-// SRC32: the caller's fp32 operands, every element rounded once per macro-tile through a second LDS image (denseGemmCvt);
+// SRC32: the caller's fp32 operands, every element rounded once per macro-tile - A's rows from registers, B's columns from
+// an fp32 LDS image - into the 16-bit LDS image the MFMAs read (denseGemmCvt);
 // otherwise the 16-bit copies (denseGemm)
 template <int KT, int PM, int NB, int MODE, bool SRC32>
 int launchGemmT(const GemmFormatDev& w, const bsmr_plan* p, const void* A, const void* B, float* P, const Queue& s) {

@@ -62,20 +62,27 @@ constexpr size_t gemmLdsBytes(int PM, int NB) { return gemmRingBytes(PM, NB) + (
 
 #if defined(BSMR_GEMM_LAB)
 // labSkip: bit 0 MFMAs, 1 fragment reads (denseGemmCvt: the rounding step), 2 DMAs, 3 slab writes, 4 entry loads, 5 stores,
-// 6 denseGemmCvt's fragment reads.  labStamps (may be null): per (workgroup, wave) eight readings of the 100 MHz clock -
-// 0 entry, 1 first stage requested, 2 own share of it landed, 3 first barrier passed, 4 K loop left, 5 + q pass q done.
+// 6 denseGemmCvt's fragment reads.  labStamps (may be null): per (workgroup, wave) ten readings of the 100 MHz clock -
+// 0 entry, 1 first stage requested, 2 own share of it landed, 3 first barrier passed, 4 K loop left, 5 + q pass q done;
+// denseGemmCvt: 8 = ticks the wave stood at the K loop's waits for its operands (summed over the slices), 9 = ticks from
+// the end of that wait to the slice's barrier passed (rounding, re-issue, barrier; summed).
+constexpr uint32_t kGemmLabStamps = 10;
 #define GEMM_LAB_ARG , uint32_t labSkip, unsigned long long* labStamps
 #define GEMM_LAB_SKIP(bit) (labSkip & (1u << (bit)))
-#define GEMM_LAB_STAMPS unsigned long long labStamp[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define GEMM_LAB_STAMPS unsigned long long labStamp[kGemmLabStamps] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, labSpan = 0
 #define GEMM_LAB_STAMP(i) labStamp[i] = __builtin_amdgcn_s_memrealtime()
+#define GEMM_LAB_SPAN_BEGIN labSpan = __builtin_amdgcn_s_memrealtime()
+#define GEMM_LAB_SPAN_END(i) labStamp[i] += __builtin_amdgcn_s_memrealtime() - labSpan
 #define GEMM_LAB_STAMPS_OUT                                                                              \
     if (labStamps && lane == 0)                                                                          \
-        for (uint32_t i = 0; i < 8u; ++i) labStamps[((size_t)blockIdx.x * kGemmWaves + wave) * 8u + i] = labStamp[i]
+        for (uint32_t i = 0; i < kGemmLabStamps; ++i) labStamps[((size_t)blockIdx.x * kGemmWaves + wave) * kGemmLabStamps + i] = labStamp[i]
 #else
 #define GEMM_LAB_ARG
 #define GEMM_LAB_SKIP(bit) false
 #define GEMM_LAB_STAMPS
 #define GEMM_LAB_STAMP(i)
+#define GEMM_LAB_SPAN_BEGIN
+#define GEMM_LAB_SPAN_END(i)
 #define GEMM_LAB_STAMPS_OUT
 #endif
 
@@ -211,9 +218,10 @@ __device__ __forceinline__ void gemmStage(const uint8_t* A, uint32_t aBytes, con
 }
 // Row id of this lane's row in a chunk of 8 rows whose ids lie at `rows8` (a wave-uniform address), written as eight loads of
 // uniform addresses and a select.  hipcc does not keep them scalar: it folds the select into the address and emits ONE
-// global_load_dword per chunk at rows8 + 4 sub (denseGemmCvt<4, 16, 20, 0>: nine, five for the B columns and four for the
-// A rows, all issued before the first DMA; each chunk's ids are then waited for with a counted vmcnt(8), (7), (7) ... in
-// front of its DMA, so no DMA waits for ids it does not need, and no id waits for a DMA).
+// global_load_dword per chunk at rows8 + 4 sub.  denseGemm issues them all before the first DMA and waits for each chunk's
+// ids with a counted vmcnt in front of its DMA, so no DMA waits for ids it does not need, and no id waits for a DMA.
+// denseGemmCvt<4, 16, 20, 0>: nine, four for the A rows and five for the B columns, beside the row table's word; the
+// fence in front of its first operand request makes them all land (vmcnt(8) .. (0)) before that request goes out.
 __device__ __forceinline__ uint32_t gemmRowOfLane(const uint32_t* __restrict__ rows8, uint32_t sub) {
     uint32_t id = rows8[0];
 #pragma unroll
@@ -423,25 +431,71 @@ denseGemm(const void* __restrict__ Aop, const void* __restrict__ Bop, uint32_t a
 // denseGemm<..., SRC32> lets every wave round the fragments it reads: the four waves of a row half round the same rows of A,
 // the two waves of a column quarter the same columns of B - 2.9 times the casts the operands need, all of them in front of
 // the MFMAs of an in-order wave (measured, nips-like K = 128: 13.4 us against 9.1 us for the kernel on 16-bit copies).  Here
-// a slice of 32 k goes through two LDS images:
-//   F  (TM + TN) rows x 128 bytes of fp32, filled by LDS-DMA, lane-linear (piece = slot: nothing reads it by fragment).  A
-//      wave's share of F is PRIVATE to it: the wave that issued the DMAs of a 1-KiB chunk is the one that rounds it, so
-//      its own counted wait orders everything and no barrier guards F;
-//   H  two stages of (TM + TN) rows x 64 bytes of fp16 / bf16 (rows of 32 k), written by the rounding step - 64 lanes read
-//      1 KiB of F linearly, round with the casts of convertOperands, write 8 bytes each - and read as MFMA fragments
-//      (ds_read_b128 of piece g of row r at slot g ^ swzH(r): conflict-free for the 16-lane groups a read is served in,
-//      as are the 8-byte writes).
-// Per slice: MFMAs of slice t from H[t & 1]; wait for the own DMAs of slice t + 1, round them into H[(t + 1) & 1], re-issue
-// the DMAs of slice t + 2 into the same chunks of F, ONE barrier (publishes H[(t + 1) & 1]; everybody's reads of it, two
-// slices ago, ended before the barrier in between).  Same casts, same MFMA, same order of k steps: bit-identical to the
-// conversion pass + 16-bit kernels.
+// a slice of 32 k is rounded once, by the wave that requested it, into a 16-bit LDS image:
+//   A  a wave's PM / 4 chunks of 8 rows x 128 bytes come into REGISTERS (buffer loads through the resource that bounds
+//      them as it bounded the DMAs: 4 registers per chunk, lane l = piece l & 7 of row l >> 3) and are rounded from there;
+//   F  B's fp32 image, TWO stages of TN rows x 128 bytes, filled by LDS-DMA, lane-linear (piece = slot: nothing reads it
+//      by fragment).  A wave's share of F is PRIVATE to it: the wave that issued the DMAs of a 1-KiB chunk is the one
+//      that rounds it, so its own counted wait orders everything and no barrier guards F;
+//   H  two stages of (TM + TN) rows x 64 bytes of fp16 / bf16 (rows of 32 k), written by the rounding step - 64 lanes take
+//      1 KiB of a slice (registers or F, read linearly), round with the casts of convertOperands, write 8 bytes each - and
+//      read as MFMA fragments (ds_read_b128 of piece g of row r at slot g ^ swzH(r): conflict-free for the 16-lane groups
+//      a read is served in, as are the 8-byte writes).
+// Requests run two slices ahead.  vmcnt is ONE in-order counter, so the order of issue is part of the design: at the end
+// of slice t a wave requests A(t + 2), THEN B(t + 3); behind the MFMAs of slice t + 1 it waits with vmcnt(NB / 4) - A(t + 2)
+// and everything older, B(t + 2) with it, have landed, the DMAs of B(t + 3) stay outstanding - rounds both into
+// H[t & 1] and re-issues.  (A second fp32 stage for A too does not fit: 2 x 72 + 72 KiB at 256 x 320.)  ONE barrier per
+// slice publishes H[(t + 1) & 1]; everybody's reads of it, two slices ago, ended before the barrier in between.  Same
+// casts, same MFMA, same order of k steps: bit-identical to the conversion pass + 16-bit kernels.
 constexpr uint32_t kGemmHalfRowBytes = 64u;                        // a row of an H stage: 32 k of 16 bits
 __host__ __device__ constexpr uint32_t gemmSwzH(uint32_t row) { return (4u - ((row >> 2) & 3u)) & 3u; }   // 0, 3, 2, 1
+// two fp32 stages of B, two 16-bit stages of both operands; reused as the eight waves' slabs by the epilogue
 constexpr uint32_t gemmCvtRingBytes(int PM, int NB) {
-    const uint32_t used = (uint32_t)(PM + NB) * 16u * (kGemmRowBytes + 2u * kGemmHalfRowBytes);
+    const uint32_t used = 2u * (uint32_t)NB * 16u * kGemmRowBytes + 2u * (uint32_t)(PM + NB) * 16u * kGemmHalfRowBytes;
     return used > kGemmWaves * kGemmSlabBytes ? used : kGemmWaves * kGemmSlabBytes;
 }
 constexpr size_t gemmCvtLdsBytes(int PM, int NB) { return gemmCvtRingBytes(PM, NB) + (size_t)PM * 16u * 4u; }
+static_assert(gemmCvtLdsBytes(16, 20) <= 160u * 1024u && gemmCvtLdsBytes(16, 16) <= 160u * 1024u && gemmCvtLdsBytes(8, 20) <= 160u * 1024u &&
+              gemmCvtLdsBytes(8, 16) <= 160u * 1024u, "the fp32 kernel's LDS fits a CU's 160 KiB");
+
+// A wave's chunks of an A slice into registers: the addresses (voff, kOff) and the bounds (the buffer resource over the
+// caller's aBytes: a piece that does not lie inside reads as zero) of the LDS-DMA form, gemmStagePart.
+template <uint32_t CHUNKS>
+__device__ __forceinline__ void gemmLoadChunks(const uint8_t* src, uint32_t srcBytes, const uint32_t* voff, uint32_t kOff, f32x4 (&v)[CHUNKS]) {
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), 0, srcBytes, 0x00020000);
+#pragma unroll
+    for (uint32_t j = 0; j < CHUNKS; ++j) v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[j], kOff, 0));
+}
+// "at most N of my younger requests are outstanding" (N is part of the instruction).  The registers the wait is for pass
+// through it: their casts are register-only, and instruction selection placed those of the K = 64 instances in front of the
+// fence and the wait, right behind the slice's first MFMA, with hipcc's own vmcnt(3) .. (0) - the wave stood there.
+template <uint32_t N, uint32_t CHUNKS>
+__device__ __forceinline__ void gemmWaitRequests(f32x4 (&landed)[CHUNKS]) {
+    static_assert(N < 64u, "vmcnt holds six bits");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (uint32_t j = 0; j < CHUNKS; ++j) asm volatile("" : "+v"(landed[j]));
+#endif
+}
+// four fp32 of a row -> 8 bytes of an H stage, the casts of convertOperands
+template <int MODE>
+__device__ __forceinline__ void gemmRoundPiece(const f32x4& v, uint8_t* dst) {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 h;
+    if constexpr (MODE == 0) {
+        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+        f16x4 o;
+        o[0] = (_Float16)v[0]; o[1] = (_Float16)v[1]; o[2] = (_Float16)v[2]; o[3] = (_Float16)v[3];
+        h = __builtin_bit_cast(u32x2, o);
+    } else {
+        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+        bf16x4 o;
+        o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
+        h = __builtin_bit_cast(u32x2, o);
+    }
+    *reinterpret_cast<u32x2*>(dst) = h;
+}
 
 template <int KT, int PM, int NB, int MODE>
 __global__ void __launch_bounds__(kGemmWaves * kWave, 2)
@@ -452,9 +506,10 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
              uint32_t gridG, uint32_t gridS, uint32_t fullGrid, Batch batch GEMM_LAB_ARG) {
     constexpr uint32_t K = 32u * KT, TM = PM * 16u, TN = NB * 16u, ROWS = TM + TN;
     constexpr uint32_t m = PM / kGemmWavesM, n = NB / kGemmWavesN, Q = (m * n + kGemmPassTiles - 1u) / kGemmPassTiles, L = kGemmWaves * Q;
-    constexpr uint32_t ADMAS = PM / 4u, BDMAS = NB / 4u, DMAS = ADMAS + BDMAS;   // 1-KiB chunks of F per wave: 8 rows each
-    constexpr uint32_t fBytes = ROWS * kGemmRowBytes, hBytes = ROWS * kGemmHalfRowBytes, bAtF = TM * kGemmRowBytes, bAtH = TM * kGemmHalfRowBytes;
-    constexpr uint32_t hAt = fBytes, rowTableAt = gemmCvtRingBytes(PM, NB);
+    constexpr uint32_t ADMAS = PM / 4u, BDMAS = NB / 4u;   // 1-KiB chunks of a slice per wave, 8 rows each: A's (registers), B's (F)
+    constexpr uint32_t fBytes = TN * kGemmRowBytes, hBytes = ROWS * kGemmHalfRowBytes, bAtH = TM * kGemmHalfRowBytes;
+    constexpr uint32_t hAt = 2u * fBytes, rowTableAt = gemmCvtRingBytes(PM, NB);
+    static_assert(hAt + 2u * hBytes <= rowTableAt, "F's two stages and H's two lie in front of the row table");
     constexpr uint32_t kGemmWordChunk = m * n > 32u ? 4u : 8u;
 
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -479,76 +534,63 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
     const uint8_t* Bb = reinterpret_cast<const uint8_t*>(Bop) + (size_t)blockIdx.y * batch.strideB * 4u;
     P += (size_t)blockIdx.y * batch.strideP;
 
-    // my chunks of F: chunk c = wave * DMAS + j holds rows 8 c .. 8 c + 7 (A's chunks first, then B's), lane l the piece l & 7
-    // (k = 4 (l & 7) .. + 3) of row 8 c + (l >> 3); where the rounded piece goes in H: row * 64 + 16 (slot) + 8 (half)
+    // my chunks of a slice: chunk c = wave * ADMAS + j of A (wave * BDMAS + j of B) holds rows 8 c .. 8 c + 7, lane l the piece
+    // l & 7 (k = 4 (l & 7) .. + 3) of row 8 c + (l >> 3); where the rounded piece goes in H: row * 64 + 16 (slot) + 8 (half)
     uint32_t voffA[ADMAS], voffB[BDMAS];
     const uint32_t piece = lane & 7u;
 #pragma unroll
-    for (uint32_t j = 0; j < BDMAS; ++j)
-        voffB[j] = gemmRowOfLane(colOf + (size_t)firstBlock * 16u + 8u * (wave * BDMAS + j), lane >> 3) * (K * 4u) + (piece << 4);
-    if (!GEMM_LAB_SKIP(2)) gemmStagePart<BDMAS>(Bb, bBytes, lds + bAtF, wave, voffB, 0u);
-#pragma unroll
     for (uint32_t j = 0; j < ADMAS; ++j)
         voffA[j] = gemmRowOfLane(panelRows + (size_t)group * TM + 8u * (wave * ADMAS + j), lane >> 3) * (K * 4u) + (piece << 4);
-    if (!GEMM_LAB_SKIP(2)) gemmStagePart<ADMAS>(Ab, aBytes, lds, wave, voffA, 0u);
+#pragma unroll
+    for (uint32_t j = 0; j < BDMAS; ++j)
+        voffB[j] = gemmRowOfLane(colOf + (size_t)firstBlock * 16u + 8u * (wave * BDMAS + j), lane >> 3) * (K * 4u) + (piece << 4);
+    // (the row table's words are asked for in front of the operands: whoever uses them then waits for nothing younger)
+    uint32_t myRowStart = 0;
+    if (threadIdx.x < TM) myRowStart = rowStart[(size_t)itemId * TM + threadIdx.x];
+    // The requests of a slice, A's THEN B's (header): the fences keep hipcc's scheduler from moving the DMAs in front of the
+    // register loads, after which its own wait for the registers would be a wait for the youngest DMAs too.
+    f32x4 aNext[ADMAS];
+#pragma unroll
+    for (uint32_t j = 0; j < ADMAS; ++j) aNext[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto requestA = [&](uint32_t slice) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (slice < (uint32_t)KT && !GEMM_LAB_SKIP(2)) gemmLoadChunks<ADMAS>(Ab, aBytes, voffA, slice * kGemmRowBytes, aNext);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto requestB = [&](uint32_t slice) {   // into F's stage slice & 1
+        __builtin_amdgcn_sched_barrier(0);
+        if (slice < (uint32_t)KT && !GEMM_LAB_SKIP(2)) gemmStagePart<BDMAS>(Bb, bBytes, lds + (slice & 1u) * fBytes, wave, voffB, slice * kGemmRowBytes);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    requestA(0u);
+    requestB(0u);
     GEMM_LAB_STAMP(1);
-    if (threadIdx.x < TM) reinterpret_cast<uint32_t*>(lds + rowTableAt)[threadIdx.x] = rowStart[(size_t)itemId * TM + threadIdx.x];
     uint32_t myList[Q + 1];
 #pragma unroll
     for (uint32_t q = 0; q <= Q; ++q) myList[q] = lists[listBase + wave * Q + q];
 
-    // rounding step: my chunks of F -> stage `to` of H.  The reads of a batch of chunks are issued together, then rounded and
-    // written: written chunk by chunk (read, round, write, read ...) every read waited for the write in front of it - the
-    // compiler cannot know that F and H do not overlap - and a wave paid nine LDS round trips in a row per slice.
-#if defined(BSMR_GEMM_ROUND_SERIAL)
-    constexpr uint32_t kRoundBatch = 1u;      // lab: one chunk at a time
-#else
-    constexpr uint32_t kRoundBatch = 5u;
-#endif
-    // (addresses: a chunk's place in F is one register per operand plus j KiB; its rows' places in H are two registers per
-    // operand - the swizzle of row 8 c + (lane >> 3) depends on c's parity only - plus j * 512 + the stage: nine source and
-    // nine destination registers, live over the whole kernel, were what the 8 x 5 tile blocks had no room for)
-    const uint32_t fOfA = wave * ADMAS * 1024u + lane * 16u, fOfB = bAtF + wave * BDMAS * 1024u + lane * 16u;
+    // rounding step: my chunks of a slice -> stage `to` of H.  B's reads of F are issued together, A's registers are rounded
+    // while they are on their way, then B's: written chunk by chunk (read, round, write, read ...) every read waited for the
+    // write in front of it - the compiler cannot know that F and H do not overlap.
+    // (addresses: a chunk's place in F is one register plus j KiB + the stage; its rows' places in H are two registers per
+    // operand - the swizzle of row 8 c + (lane >> 3) depends on c's parity only - plus j * 512 + the stage)
+    const uint32_t fOfB = wave * BDMAS * 1024u + lane * 16u;
     auto hOf = [&](uint32_t part, uint32_t firstChunk, uint32_t odd) {
         const uint32_t quarter = (2u * (firstChunk + odd) + (lane >> 5)) & 3u;            // (row >> 2) & 3 of the lane's row
         return hAt + part + firstChunk * 512u + (lane >> 3) * kGemmHalfRowBytes + (((piece >> 1) ^ ((4u - quarter) & 3u)) << 4) + ((piece & 1u) << 3);
     };
     const uint32_t hOfA[2] = {hOf(0u, wave * ADMAS, 0u), hOf(0u, wave * ADMAS, 1u)};
     const uint32_t hOfB[2] = {hOf(bAtH, wave * BDMAS, 0u), hOf(bAtH, wave * BDMAS, 1u)};
-    auto roundChunks = [&](uint32_t to) {
+    auto roundChunks = [&](uint32_t slice) {
         if (GEMM_LAB_SKIP(1)) return;
+        const uint32_t to = (slice & 1u) * hBytes;
+        f32x4 v[BDMAS];
 #pragma unroll
-        for (uint32_t j0 = 0; j0 < DMAS; j0 += kRoundBatch) {
-            f32x4 v[kRoundBatch];
+        for (uint32_t j = 0; j < BDMAS; ++j) v[j] = *reinterpret_cast<const f32x4*>(lds + (slice & 1u) * fBytes + fOfB + j * 1024u);
 #pragma unroll
-            for (uint32_t b = 0; b < kRoundBatch; ++b) {
-                const uint32_t j = j0 + b;
-                if (j >= DMAS) continue;
-                v[b] = j < ADMAS ? *reinterpret_cast<const f32x4*>(lds + fOfA + j * 1024u)
-                                 : *reinterpret_cast<const f32x4*>(lds + fOfB + (j - ADMAS) * 1024u);
-            }
+        for (uint32_t j = 0; j < ADMAS; ++j) gemmRoundPiece<MODE>(aNext[j], lds + hOfA[j & 1u] + j * 512u + to);
 #pragma unroll
-            for (uint32_t b = 0; b < kRoundBatch; ++b) {
-                const uint32_t j = j0 + b;
-                if (j >= DMAS) continue;
-                const uint32_t jj = j < ADMAS ? j : j - ADMAS;
-                uint8_t* dst = lds + (j < ADMAS ? hOfA[jj & 1u] : hOfB[jj & 1u]) + jj * 512u + to * hBytes;
-                typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-                u32x2 h;
-                if constexpr (MODE == 0) {
-                    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-                    f16x4 o;
-                    o[0] = (_Float16)v[b][0]; o[1] = (_Float16)v[b][1]; o[2] = (_Float16)v[b][2]; o[3] = (_Float16)v[b][3];
-                    h = __builtin_bit_cast(u32x2, o);
-                } else {
-                    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-                    bf16x4 o;
-                    o[0] = (__bf16)v[b][0]; o[1] = (__bf16)v[b][1]; o[2] = (__bf16)v[b][2]; o[3] = (__bf16)v[b][3];
-                    h = __builtin_bit_cast(u32x2, o);
-                }
-                *reinterpret_cast<u32x2*>(dst) = h;
-            }
-        }
+        for (uint32_t j = 0; j < BDMAS; ++j) gemmRoundPiece<MODE>(v[j], lds + hOfB[j & 1u] + j * 512u + to);
     };
 
     // fragment addresses in an H stage: piece g of row / column r at slot g ^ swzH(r)
@@ -562,10 +604,12 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
 #pragma unroll
         for (uint32_t j = 0; j < n; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     // entry words as in denseGemm: pass 0's first trip rides along with the first stage's round trip where the loop is short
+    // (not in the 8 x 5 tile blocks: with A's 16 registers carried through the MFMAs the four words were spilled, and a
+    // spill's store and reload count on vmcnt; they request them at the top of the last slice)
     auto loadWords = [&](uint32_t e0, uint32_t (&w)[kGemmWordChunk]) { gemmLoadWords<kGemmWordChunk>(words, e0, lane, w, GEMM_LAB_SKIP(4)); };
     constexpr bool kDeepWords = Q >= 2u && m * n <= 32u;
     uint32_t wAhead[2][kGemmWordChunk];
-    constexpr bool kEarlyWords = KT <= 4;
+    constexpr bool kEarlyWords = KT <= 4 && m * n <= 32u;
     auto firstWords = [&]() {
         loadWords(myList[0], wAhead[0]);
         if (kDeepWords) loadWords(myList[1], wAhead[1]);
@@ -574,12 +618,16 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
     if (kEarlyWords) firstWords();
 #endif
 
-    // slice 0: landed (my chunks), rounded into H[0], slice 1 requested, H[0] published
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // slice 0: B(1) requested behind the entry words, so that the wait below leaves nothing but B(1) outstanding; A(0) and
+    // B(0) landed (my chunks), rounded into H[0]; A(1), then B(2) requested; H[0] published
+    requestB(1u);
+    if (KT > 1) gemmWaitRequests<BDMAS>(aNext); else gemmWaitRequests<0>(aNext);
     GEMM_LAB_STAMP(2);
+    if (threadIdx.x < TM) reinterpret_cast<uint32_t*>(lds + rowTableAt)[threadIdx.x] = myRowStart;   // (read behind the K loop's barriers)
     roundChunks(0u);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (KT > 1 && !GEMM_LAB_SKIP(2)) gemmStage<ADMAS, BDMAS>(Ab, aBytes, Bb, bBytes, lds, bAtF, wave, voffA, voffB, kGemmRowBytes);
+    requestA(1u);
+    requestB(2u);
     __builtin_amdgcn_s_barrier();
     GEMM_LAB_STAMP(3);
 #if defined(BSMR_GEMM_LATE_WORDS)
@@ -588,7 +636,10 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
 
 #pragma unroll
     for (uint32_t t = 0; t < (uint32_t)KT; ++t) {
-        if (!kEarlyWords && t + 1u == (uint32_t)KT) firstWords();
+        if (!kEarlyWords && t + 1u == (uint32_t)KT) {   // (fenced: hipcc sank the requests behind the slice's MFMAs)
+            firstWords();
+            __builtin_amdgcn_sched_barrier(0);
+        }
         const uint8_t* base = lds + hAt + (t & 1u) * hBytes;
         u32x4 bf[n];
 #pragma unroll
@@ -596,6 +647,18 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
             bf[j] = GEMM_LAB_SKIP(6) ? u32x4{lane, t, j, 0u} : *reinterpret_cast<const u32x4*>(base + bRead + j * 16u * kGemmHalfRowBytes);
 #pragma unroll
         for (uint32_t i = 0; i < m; ++i) {
+            if (i + 1u == m && t + 1u < (uint32_t)KT) {
+                // my chunks of slice t + 1 have landed - A(t + 1) and, requested before it, B(t + 1); B(t + 2)'s DMAs stay
+                // outstanding.  The last wait of the loop is vmcnt(0): nothing is on its way when the epilogue takes the
+                // LDS.  (MFMAs are register-only: without the fence hipcc moves the wait, and its own waits for A's
+                // registers, in front of the slice's MFMAs - the wave then stands there with nothing issued.  The last
+                // row tile's MFMAs stay behind the wait and run beside the rounding.)
+                __builtin_amdgcn_sched_barrier(0);
+                GEMM_LAB_SPAN_BEGIN;
+                if (t + 2u < (uint32_t)KT) gemmWaitRequests<BDMAS>(aNext); else gemmWaitRequests<0>(aNext);
+                GEMM_LAB_SPAN_END(8);
+                GEMM_LAB_SPAN_BEGIN;
+            }
             const u32x4 af = GEMM_LAB_SKIP(6) ? u32x4{lane, t, i, 2u} : *reinterpret_cast<const u32x4*>(base + aRead + i * 16u * kGemmHalfRowBytes);
             if (!GEMM_LAB_SKIP(0)) {
 #pragma unroll
@@ -607,16 +670,18 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
             }
         }
         if (t + 1u < (uint32_t)KT) {
-            // my chunks of slice t + 1 have landed: round them into the other stage of H, then F takes slice t + 2
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            roundChunks((t + 1u) & 1u);
+            // round them into the other stage of H, then the registers take A(t + 2) and the stage of F just read (this
+            // wave's own reads of it are over: lgkmcnt(0)) takes B(t + 3)
+            roundChunks(t + 1u);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (t + 2u < (uint32_t)KT && !GEMM_LAB_SKIP(2))
-                gemmStage<ADMAS, BDMAS>(Ab, aBytes, Bb, bBytes, lds, bAtF, wave, voffA, voffB, (t + 2u) * kGemmRowBytes);
+            requestA(t + 2u);
+            requestB(t + 3u);
         } else {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            GEMM_LAB_SPAN_BEGIN;
         }
         __builtin_amdgcn_s_barrier();
+        GEMM_LAB_SPAN_END(9);
     }
 
     // ---- the sparse mask: slab passes over the wave's tiles (as denseGemm)

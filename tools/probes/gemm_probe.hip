@@ -40,7 +40,7 @@ struct Variant {
     int KT, PM, NB, mode;
     bool src32;
     Kernel kernel;
-    bool shared = false;   // denseGemmCvt: one rounding per element through a second LDS image
+    bool shared = false;   // denseGemmCvt: one rounding per element (A from registers, B from an fp32 LDS image) into a 16-bit LDS image
 };
 #define V(name, KT, PM, NB, MODE) {name, KT, PM, NB, MODE, false, bsmr::denseGemm<KT, PM, NB, MODE, false>}
 #define V32(name, KT, PM, NB, MODE) {name, KT, PM, NB, MODE, true, bsmr::denseGemm<KT, PM, NB, MODE, true>}
@@ -58,6 +58,7 @@ static const Variant kVariants[] = {
     // fp32 operands, one shared rounding per element (denseGemmCvt)
     VC("k128_cvt_256x256", 4, 16, 16, 0), VC("k128_cvt_256x320", 4, 16, 20, 0), VC("k128_cvt_128x256", 4, 8, 16, 0),
     VC("k128_cvt_128x320", 4, 8, 20, 0), VC("k64_cvt_256x320", 2, 16, 20, 0), VC("k128_cvtb_256x320", 4, 16, 20, 1),
+    VC("k64_cvt_256x256", 2, 16, 16, 0), VC("k64_cvt_128x256", 2, 8, 16, 0), VC("k64_cvt_128x320", 2, 8, 20, 0),
     VC("k32_cvt_256x320", 1, 16, 20, 0), VC("k512_cvtb_256x256", 16, 16, 16, 1), VC("k256_cvt_256x256", 8, 16, 16, 0),
     VC("k512_cvtb_256x320", 16, 16, 20, 1), VC("k512_cvt_256x320", 16, 16, 20, 0),
 };
@@ -215,7 +216,7 @@ int main(int argc, char** argv) {
     }
 #ifdef BSMR_GEMM_LAB
     {   // one launch with clock readings (100 MHz): where the waves are when, relative to the first wave's entry
-        const size_t count = f.items.size() * 8 * 8;
+        const size_t NS = bsmr::kGemmLabStamps, count = f.items.size() * 8 * NS;
         unsigned long long* dStamps;
         CHECK(hipMalloc(&dStamps, count * 8));
         CHECK(hipMemset(dStamps, 0, count * 8));
@@ -227,25 +228,36 @@ int main(int argc, char** argv) {
         std::vector<unsigned long long> st(count);
         CHECK(hipMemcpy(st.data(), dStamps, count * 8, hipMemcpyDeviceToHost));
         unsigned long long t0 = ~0ull;
-        for (size_t w = 0; w < count / 8; ++w) t0 = std::min(t0, st[w * 8]);
+        for (size_t w = 0; w < count / NS; ++w) t0 = std::min(t0, st[w * NS]);
         static const char* kNames[8] = {"entry", "first stage requested", "own share landed", "first barrier passed", "K loop left", "pass 0 done", "pass 1 done", "pass 2 done"};
-        printf("  clock readings over %zu waves, us after the first wave's entry (min / mean / max):\n", count / 8);
+        printf("  clock readings over %zu waves, us after the first wave's entry (min / mean / max):\n", count / NS);
         for (int i = 0; i < 8; ++i) {
             double lo = 1e30, hi = 0, sum = 0;
             size_t seen = 0;
-            for (size_t w = 0; w < count / 8; ++w) {
-                if (!st[w * 8 + i]) continue;
-                const double us = (double)(st[w * 8 + i] - t0) * 0.01;
+            for (size_t w = 0; w < count / NS; ++w) {
+                if (!st[w * NS + i]) continue;
+                const double us = (double)(st[w * NS + i] - t0) * 0.01;
                 lo = std::min(lo, us); hi = std::max(hi, us); sum += us; ++seen;
             }
             if (seen) printf("    %-22s %6.2f %6.2f %6.2f\n", kNames[i], lo, sum / seen, hi);
+        }
+        {   // the K loop per slice: first barrier passed -> loop left, and denseGemmCvt's two spans inside it (means over the waves)
+            double loop = 0, wait = 0, rest = 0;
+            for (size_t w = 0; w < count / NS; ++w) {
+                loop += (double)(st[w * NS + 4] - st[w * NS + 3]) * 0.01;
+                wait += (double)st[w * NS + 8] * 0.01;
+                rest += (double)st[w * NS + 9] * 0.01;
+            }
+            const double per = 1.0 / ((double)(count / NS) * v->KT);
+            printf("    per slice (%d slices): period %.3f us, at the operand wait %.3f us, wait's end -> barrier passed %.3f us\n", v->KT,
+                   loop * per, wait * per, rest * per);
         }
         // the workgroups' last readings, sorted: how the launch drains
         std::vector<double> ends;
         for (size_t g = 0; g < f.items.size(); ++g) {
             unsigned long long e = 0;
             for (size_t w = 0; w < 8; ++w)
-                for (int i = 4; i < 8; ++i) e = std::max(e, st[(g * 8 + w) * 8 + i]);
+                for (int i = 4; i < 8; ++i) e = std::max(e, st[(g * 8 + w) * NS + i]);
             ends.push_back((double)(e - t0) * 0.01);
         }
         std::sort(ends.begin(), ends.end());
