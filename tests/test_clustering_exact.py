@@ -11,6 +11,7 @@ import pytest
 import synth
 
 import bsmr_oracle as bo
+import cluster_patterns as cp
 
 
 def clustered_pattern(rows, cols, groups, per_row, seed, noise=0.3):
@@ -132,3 +133,111 @@ def test_numpy_restatement_on_small_input(engine, oracle):
         perm, clusters = oracle.bsa_row_reordering(rows, cols, ro, ci, 16, alpha)
         rr, nc = bo.row_reordering(rows, cols, ro, ci, alpha, 16)
         assert np.array_equal(rr, perm) and nc == clusters
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Ties with alpha, pairs exactly on alpha, a representative whose squared norm wraps (tests/cluster_patterns.py)
+# ------------------------------------------------------------------------------------------------------------------------
+def oracle_result(oracle, name):
+    rows, cols, ro, ci, bw, alpha = cp.case_pattern(name)
+    return oracle.bsa_row_reordering(rows, cols, ro, ci, bw, alpha)
+
+
+def test_bins_that_count_restated(oracle):
+    for nb in (20, 300, 520, 768, 800, 1250, 4500):
+        assert np.array_equal(cp.live_bins(nb), oracle.cluster_bin_mask(nb)), nb
+
+
+@pytest.mark.parametrize("name", list(cp.ALL_CASES))
+def test_host_pipeline_on_ties_and_wrapped_norms(engine, oracle, name):
+    """The case meets its own conditions (>= 5 flips, >= 2 at 1 250 bins; >= 1 000 pairs on alpha; >= 500 comparisons with
+    a wrapped norm and a first cluster of exactly 256 rows), and the host pipeline gives the C oracle's row order and
+    cluster count on it.
+
+    Census of the reference's sequential run per case (numpy restatement; `near` = float64 quotient within 1e-4 of alpha,
+    `equal` = fp32 similarity == alpha, `flips` = fp32 block-order verdict differs from the float64 one, `wrapped` = the
+    representative's true sum of squares is >= 2^32; clusters = number of clusters formed):
+      case                 alpha                  comparisons  near   equal  flips  wrapped  clusters
+      b20-s4-third         nextafter(f32(1/3),0)          394    18      13     13        0         6
+      b20-s46-half         0.5                           1096    18      14      8        0        22
+      b300-s4-third        nextafter(f32(1/3),0)          385    16       6      6        0         6
+      b300-s46-third       nextafter(f32(1/3),0)          271    17       5      5        0         5
+      b1250-s4-half        0.5 (seed 2)                  1822    77      77      3        0        28
+      b20-s4-sixtenths     f32(0.6)                      8984  1460    1460      0        0       100
+      b300-s4-sixtenths    f32(0.6)                      8984  1460    1460      0        0       100
+      wrap-0.3, wrap-0.9   0.3, 0.9                      1329     0       0      0      632         3 (256, 256, 188 rows)
+    """
+    rows, cols, ro, ci, bw, alpha = cp.case_pattern(name)
+    cp.assert_case_is_loaded(name, cp.case_census(name))
+    want, want_clusters = oracle_result(oracle, name)
+    pipe = engine.Pipeline(engine.CSR.from_arrays(rows, cols, ro, ci), alpha=alpha, delta=0.3, block_size=bw, device=-1)
+    assert np.array_equal(pipe.array("reorderedRows"), want)
+    assert pipe.num_clusters == want_clusters
+
+
+@pytest.mark.parametrize("name", [n for n in cp.ALL_CASES if n.startswith(("b20-", "wrap-"))])
+def test_numpy_restatement_on_ties_and_wrapped_norms(oracle, name):
+    """bsmr_oracle.row_reordering and the census' own walk equal the C oracle; the census is the same whether the fp32
+    similarity comes from numpy or from C"""
+    rows, cols, ro, ci, bw, alpha = cp.case_pattern(name)
+    want, want_clusters = oracle_result(oracle, name)
+    rr, nc = bo.row_reordering(rows, cols, ro, ci, alpha, bw)
+    assert np.array_equal(rr, want) and nc == want_clusters
+    perm, clusters, census = cp.sequential_clustering(rows, cols, ro, ci, alpha, bw, "reference", oracle.cluster_similarity)
+    assert np.array_equal(perm, want) and clusters == want_clusters
+    assert census == cp.case_census(name)
+
+
+def defect_differs(oracle, name, verdict):
+    rows, cols, ro, ci, bw, alpha = cp.case_pattern(name)
+    want, want_clusters = oracle_result(oracle, name)
+    # the walk itself is the oracle's: only the verdict can make the difference below
+    perm, clusters, _ = cp.sequential_clustering(rows, cols, ro, ci, alpha, bw, "reference", oracle.cluster_similarity)
+    assert np.array_equal(perm, want) and clusters == want_clusters
+    perm, clusters, _ = cp.sequential_clustering(rows, cols, ro, ci, alpha, bw, verdict, oracle.cluster_similarity)
+    return not np.array_equal(perm, want) or clusters != want_clusters
+
+
+@pytest.mark.parametrize("name", cp.FLIP_CASES)
+def test_a_float64_verdict_fails_the_flip_cases(oracle, name):
+    """an implementation that never re-evaluated pairs near alpha in the reference's fp32 order would not pass"""
+    assert defect_differs(oracle, name, "float64")
+
+
+@pytest.mark.parametrize("name", cp.EQUAL_CASES)
+def test_greater_equal_fails_the_cases_on_alpha(oracle, name):
+    assert defect_differs(oracle, name, "greater_equal")
+
+
+@pytest.mark.parametrize("name", list(cp.WRAP_CASES))
+def test_a_64_bit_norm_fails_the_wrap_cases(oracle, name):
+    """with a squared norm that does not wrap all 700 rows form one cluster"""
+    rows, cols, ro, ci, bw, alpha = cp.case_pattern(name)
+    perm, clusters, census = cp.sequential_clustering(rows, cols, ro, ci, alpha, bw, "norm64", oracle.cluster_similarity)
+    assert census["cluster_sizes"] == [700]
+    assert defect_differs(oracle, name, "norm64")
+
+
+def limit_pattern(bins, bw=16, rows=48, seed=9):
+    """48 rows around 3 column prototypes over bins * bw columns; every third row also holds the last column"""
+    cols = bins * bw
+    _, _, ro, ci = clustered_pattern(rows, cols, 3, 12, seed)
+    per = [ci[ro[r]:ro[r + 1]] for r in range(rows)]
+    for r in range(0, rows, 3):
+        per[r] = np.union1d(per[r], [cols - 1]).astype(np.uint32)
+    ro = np.zeros(rows + 1, dtype=np.uint32)
+    ro[1:] = np.cumsum([c.size for c in per])
+    return rows, cols, ro, np.concatenate(per).astype(np.uint32)
+
+
+@pytest.mark.parametrize("bins", [40944, 40945])
+def test_host_pipeline_around_the_device_histogram_limit(engine, oracle, bins):
+    """40 944 bins is the largest row histogram bsmr_cluster_rows takes (numBins * 4 <= 160 KiB - 64); from 40 945 on the
+    pipeline clusters on the host.  The host implementation equals the oracle on both sides (tests/test_gpu_cluster.py
+    runs the device on them)."""
+    rows, cols, ro, ci = limit_pattern(bins)
+    assert int(ci.max()) // 16 == bins - 1
+    for alpha in (0.1, 0.3):
+        want, want_clusters = oracle.bsa_row_reordering(rows, cols, ro, ci, 16, alpha)
+        pipe = engine.Pipeline(engine.CSR.from_arrays(rows, cols, ro, ci), alpha=alpha, delta=0.3, block_size=16, device=-1)
+        assert np.array_equal(pipe.array("reorderedRows"), want) and pipe.num_clusters == want_clusters
