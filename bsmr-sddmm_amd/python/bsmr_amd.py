@@ -254,6 +254,9 @@ HIP_SYMBOLS = {
                                        [C.c_uint32, C.c_void_p]),
     "bsmr_sparse_attention_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
                                           [C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bsmr_sparse_attention_qkv_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
+                                     [C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_widen_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
     "bsmr_sddmm_b8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
                                 C.c_void_p]),
@@ -922,6 +925,20 @@ def sparse_attention_backward(bw, Kv: int, scale: float, P_ptr: int, m_ptr: int,
         _check(hip().bsmr_sparse_attention_backward(*args, stream), "bsmr_sparse_attention_backward")
     else:
         _check(hip().bsmr_sparse_attention_backward_16(*args, mode, stream), "bsmr_sparse_attention_backward_16")
+
+
+# --- one-pass sparse attention: O = softmax_rows(scale Q Kt^T over S) V in a single gather, no scores stored ---
+def sparse_attention_qkv_reserve(bw, K: int, Kv: int, num_batches: int = 1):
+    """workspace of sparse_attention_qkv_16 with (K, Kv, num_batches): the chunk partials of the split rows"""
+    _check(hip().bsmr_sparse_attention_qkv_reserve(bw, K, Kv, num_batches), "bsmr_sparse_attention_qkv_reserve")
+
+
+def sparse_attention_qkv_16(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt_ptr: int, V_ptr: int, O_ptr: int, m_ptr: int,
+                            s_ptr: int, num_batches: int = 1, stream: int = 0, mode=COMPUTE_F16):
+    """O, m and s from fp16 / bf16 Q, Kt and V (all of mode's format) with an online softmax; K, Kv multiples of 32 up to 512"""
+    _check(hip().bsmr_sparse_attention_qkv_16(bw, K, Kv, scale, Q_ptr or None, Kt_ptr or None, V_ptr or None, O_ptr or None,
+                                              m_ptr or None, s_ptr or None, num_batches, mode, stream),
+           "bsmr_sparse_attention_qkv_16")
 
 
 # --- fp8 keys and values: the column-side operand as OCP fp8 bytes (fmt FP8_E4M3 / FP8_E5M2), widened exactly to the

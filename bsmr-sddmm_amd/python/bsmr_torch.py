@@ -123,6 +123,7 @@ _MODE8 = {torch.float8_e4m3fn: eng.FP8_E4M3, torch.float8_e5m2: eng.FP8_E5M2}
 _EMAX8 = {torch.float8_e4m3fn: 8, torch.float8_e5m2: 15}   # exponent of the largest normal: 448 = 1.75 2^8, 57344 = 1.75 2^15
 _SCALE_DTYPES = (torch.uint8,) + ((torch.float8_e8m0fnu,) if hasattr(torch, "float8_e8m0fnu") else ())
 MX_BLOCK = 32
+ONE_PASS_MAX_K = 512   # attention(one_pass=True): one wave holds a whole row of Q (K) and of the accumulators (Kv)
 _FP4 = getattr(torch, "float4_e2m1fn_x2", None)   # two e2m1 codes per byte, element 2i in the low nibble
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # the magnitude of code 0 .. 7; bit 3 is the sign
 _E2M1_TIES = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)   # the midpoint between codes i and i + 1
@@ -305,12 +306,19 @@ class SparseOperator:
         return _SoftmaxSpMM.apply(self, values, X, scale)
 
     def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None, fused: bool = False,
-                  out_dtype=None, Kt_scale=None, V_scale=None) -> torch.Tensor:
+                  out_dtype=None, Kt_scale=None, V_scale=None, one_pass: bool = False) -> torch.Tensor:
         """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
         positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row.
         fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order.
         Kt and V may each be fp8 or fp4; out_dtype (default Q.dtype) is the result's dtype when V is, unused otherwise.
-        Kt_scale / V_scale: the MX block scales of an fp8 Kt / V, independently of each other."""
+        Kt_scale / V_scale: the MX block scales of an fp8 Kt / V, independently of each other.
+        one_pass=True: the same function in one kernel with an online softmax (bsmr_sparse_attention_qkv_16) - the scores
+        are never stored in the forward; Q, Kt, V fp16 or bf16 of one dtype, K and Kv at most 512, no scales, no out_dtype."""
+        if one_pass:
+            if fused:
+                raise ValueError("fused=True with one_pass=True: they are two different paths, choose one")
+            self._check_one_pass(Q, Kt, V, out_dtype, Kt_scale, V_scale)
+            return _AttentionOnePass.apply(self, Q, Kt, V, Q.shape[-1] ** -0.5 if scale is None else scale)
         self._no_scale(None if _is8(Kt) or _is4(Kt) else Kt_scale, "Kt_scale", "Kt")   # both refused before any device work
         self._no_scale(None if _is8(V) or _is4(V) else V_scale, "V_scale", "V")
         if _is4(V):
@@ -602,6 +610,44 @@ class SparseOperator:
                              self._stream(), mode=_MODE16.get(X.dtype, eng.COMPUTE_F32))
         return O, m, s
 
+    @staticmethod
+    def _check_one_pass(Q, Kt, V, out_dtype, Kt_scale, V_scale):
+        """the limits of attention(one_pass=True), named before any device work"""
+        for t, name in ((Q, "Q"), (Kt, "Kt"), (V, "V")):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}: expected a torch.Tensor")
+            if t.dtype not in _MODE16:
+                raise ValueError(f"{name}: dtype {t.dtype} - one_pass=True takes torch.float16 or torch.bfloat16 operands only "
+                                 "(fp32, fp8 and fp4 go through one_pass=False)")
+            if t.dtype != Q.dtype:
+                raise ValueError(f"{name}: dtype {t.dtype} beside Q's {Q.dtype} - one_pass=True needs one dtype for Q, Kt and V")
+            if t.dim() in (2, 3) and not 32 <= t.shape[-1] <= ONE_PASS_MAX_K:
+                raise ValueError(f"{name}: {t.shape[-1]} features - one_pass=True takes K and Kv in 32 ... {ONE_PASS_MAX_K}")
+        if Kt_scale is not None or V_scale is not None:
+            raise ValueError("Kt_scale / V_scale: one_pass=True takes no MX block scales (no fp8 or fp4 operands)")
+        if out_dtype is not None:
+            raise ValueError("out_dtype: one_pass=True gives Q's dtype and takes no out_dtype")
+
+    def _attention_qkv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale):
+        """(O, m, s) of the one-pass forward; O (M, Kv) or (b, M, Kv) in Q's dtype, m and s (M,) or (b, M) fp32"""
+        b, K = self._check(Q, "Q", self.M, None)
+        _, K2 = self._check(Kt, "Kt", self.N, (b,))
+        _, Kv = self._check(V, "V", self.N, (b,))
+        if K2 != K:
+            raise ValueError(f"Q and Kt disagree on K ({K} vs {K2})")
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"scale: {scale!r} is not a number") from None
+        if not math.isfinite(scale):
+            raise ValueError(f"scale: {scale} is not finite")
+        O = torch.empty((self.M, Kv) if b is None else (b, self.M, Kv), dtype=Q.dtype, device=self.device)
+        m = torch.empty((self.M,) if b is None else (b, self.M), dtype=torch.float32, device=self.device)
+        s = torch.empty_like(m)
+        eng.sparse_attention_qkv_16(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(),
+                                    m.data_ptr(), s.data_ptr(), b or 1, self._stream(), mode=_MODE16[Q.dtype])
+        return O, m, s
+
     def _attention_backward(self, v, m, s, dW, O, dO, scale):
         """(dP, W) of the fused backward; dP is written over dW (the same tensor is returned)"""
         b, K = self._check(O, "O", self.M, None)
@@ -815,6 +861,34 @@ class _SoftmaxSpMM(torch.autograd.Function):
         dP, W = op._attention_backward(values, m, s, op._sddmm(dO, X), O, dO, ctx.scale)
         dX = op._spmm(W, dO, True) if need_x else None
         return None, dP if need_v else None, dX, None
+
+
+class _AttentionOnePass(torch.autograd.Function):
+    """attention(one_pass=True): the forward stores no score; the backward recomputes P = sddmm(Q, Kt) and then is the
+    backward of _SoftmaxSpMM behind the backward of _SDDMM, from calls the engine already has"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, Q, Kt, V, scale):
+        O, m, s = op._attention_qkv(Q, Kt, V, scale)
+        ctx.op, ctx.scale = op, float(scale)
+        ctx.save_for_backward(Q, Kt, V, O, m, s)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        op = ctx.op
+        need_q, need_k, need_v = ctx.needs_input_grad[1:4]
+        if not (need_q or need_k or need_v):
+            return None, None, None, None, None
+        Q, Kt, V, O, m, s = ctx.saved_tensors
+        dO = _grad(dO, V.dtype)
+        P = op._sddmm(Q, Kt)   # the scores exist only from here on
+        dP, W = op._attention_backward(P, m, s, op._sddmm(dO, V), O, dO, ctx.scale)
+        dV = op._spmm(W, dO, True) if need_v else None
+        dQ = dKt = None
+        if need_q or need_k:
+            dQ, dKt = op._sddmm_backward(dP, Q, Kt, need_q, need_k)
+        return None, dQ, dKt, dV, None
 
 
 class _SoftmaxSpMM8(torch.autograd.Function):

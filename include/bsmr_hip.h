@@ -742,6 +742,54 @@ int bsmr_sparse_attention_backward_16(bsmr_backward *bw, uint32_t Kv, float scal
                                       const void *dO16_dev, float *dP_dev, float *W_dev, uint32_t num_batches,
                                       int compute_mode, void *stream);
 
+/* ---- One-pass sparse attention: Q Kt^T, softmax and . V in a single gather (revision 5, added without any layout change) ----
+ * O = softmax_rows(scale Q Kt^T at S's stored positions) V with no score ever stored: nothing of size nnz is written, read
+ * or allocated.  Same handle, row lists and row chunk table as bsmr_spmm (transpose 0) and bsmr_sparse_attention.
+ * Q [b][M][K], Kt [b][N][K], V [b][N][Kv], O [b][M][Kv] are fp16 or bf16, all of compute_mode's format (BSMR_COMPUTE_F16 /
+ * _BF16); m and s [b][M] are fp32.  K and Kv are multiples of 32 in 32 ... 512, anything else is BSMR_ERR_UNSUPPORTED_K:
+ * the upper limit is this kernel's - one wave holds a whole row of Q and a whole row of accumulators.
+ * Per row r with entries t in CSR order and columns c_t (u = 2^-24, every step one IEEE fp32 operation, the accurate expf):
+ *   p_t = sum_k Q[r,k] Kt[c_t,k]: the operands widened exactly, in this order - lane j of 4 owns the elements
+ *         k = 32 i + 8 j ... 32 i + 8 j + 7 for i = 0 ... K/32 - 1 and runs ONE accumulator from +0 over them in ascending
+ *         k, two elements per step (v_dot2_f32_f16 / _bf16: exact products, fp32 accumulation); the four partials are
+ *         added as (x0 + x1) + (x2 + x3).  At most K/8 + 2 roundings per term.
+ *   z_t = fl(scale p_t).
+ *   The entries are taken in tiles of 16 consecutive entries with a running maximum m (from -inf), sum s and row acc (from
+ *   +0).  Before a tile: m' = max(m, tile max); alpha = expf(fl(m - m')) (1 while m = -inf); s = fl(s alpha), acc =
+ *   fl(acc alpha) (skipped when m' = m: alpha is 1); then in entry order e_t = expf(fl(z_t - m')) (0 while m' = -inf),
+ *   s = s + e_t, acc_k = fmaf(e_t, V[c_t,k], acc_k).  A NaN z makes m NaN from its tile on (the flag rule of "Sparse row
+ *   softmax").
+ *   A row longer than BSMR_BACKWARD_CHUNK is the handle's chunks; each gives (m_c, s_c, acc_c) as above, merged in chunk
+ *   order: m = max_c m_c (NaN if any is), beta_c = expf(fl(m_c - m)) (0 when m_c = -inf), s = sum_c fl(s_c beta_c),
+ *   acc = sum_c fl(acc_c beta_c), from +0.  A chunk with m_c = -inf is skipped rather than multiplied by 0, and so are
+ *   the entries of a tile met while m is still -inf: a non-finite row of V behind such scores does not reach O (finite
+ *   rows of V: the same bits).
+ *   O_k = round16(acc_k / s): one IEEE division, one rounding (the casts of bsmr_convert_operands).
+ * m and s are the final row maximum and sum: bsmr_sparse_attention_backward_16 accepts them as they are, with P recomputed
+ * by bsmr_sddmm_16 (whose scores differ from p_t in the last bits: a relative 2 |dz| on w, the score term below once more).
+ * An empty row, or one whose scores are all -inf, gives O = +0 exactly, m = -inf, s = 0.  A NaN or +inf score makes that
+ * row of O NaN and no other.  A row with one finite entry returns that row of V bit for bit.  A row whose scores are all
+ * equal returns round16(fl(sum of its V rows) / n) with s = n exactly (every alpha, beta and e is 1).
+ * No atomics, one writer per element: bitwise reproducible call to call, stream to stream, batch to batch and for any
+ * row_order.
+ * Forward bound against fp64 on the same 16-bit inputs.  With A_t = sum_k |Q[r,k]| |Kt[c_t,k]|,
+ * d = |scale| (K + 1) u max_t A_t (the score term: |z_t - z64_t| <= d), Z_r = max_t |z_t - m|, T = min(ceil(n / 16), 32)
+ * the tiles an entry's chunk has at most, w64 the fp64 weights and u16 = 2^-11 (fp16) or 2^-8 (bf16):
+ *   |O_k - O64_k| <= [(exp(2 d) - 1) + exp(2 d) (2 n + 6 T + 2 Z_r + 13) u] sum_t w64_t |V[c_t,k]|
+ *                    + (n + 2 T + 2) 2^-126 max_t |V[c_t,k]|, and then the one rounding: + u16 |O_k| (+ 2^-25 in fp16);
+ *   |m - m64| <= d;   |s - s64| <= [(exp(2 d) - 1) + exp(2 d) (n + 3 T + Z_r + 7) u] s64.
+ * Workspace: the chunk partial rows [b][slots][Kv], then s_c and m_c [b][slots]; bsmr_sparse_attention_qkv_reserve(K, Kv,
+ * num_batches) sizes it, afterwards covered calls allocate nothing.  The layouts and reserves of every other call are
+ * unchanged.
+ * Checked before any device call, in this order: a NULL handle or a non-finite scale (BSMR_ERR_INVALID_ARG), K or Kv
+ * (BSMR_ERR_UNSUPPORTED_K), compute_mode, more than 65535 batches, then the pointers: 16 bytes for Q, Kt, V and O, 4 for m
+ * and s.  num_batches = 0 is a no-op.  With nnz = 0 the inputs may be NULL and the call writes O = +0, m = -inf, s = 0.
+ * Every row, batch and workspace offset is formed in 64 bits. */
+int bsmr_sparse_attention_qkv_reserve(bsmr_backward *bw, uint32_t K, uint32_t Kv, uint32_t num_batches);
+int bsmr_sparse_attention_qkv_16(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                 const void *Kt16_dev, const void *V16_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                 uint32_t num_batches, int compute_mode, void *stream);
+
 /* ---- fp8 keys and values (revision 5, added without any layout change; no reference counterpart) ----
  * The column-side operand - B / Kt of the SDDMM, X / V of the SpMM and of the fused attention - may be OCP fp8, one byte per
  * element, as an fp8 KV cache holds it: fp8_format BSMR_FP8_E4M3 (e4m3fn: no infinity, two NaN codes) or BSMR_FP8_E5M2 (two

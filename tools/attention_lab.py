@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""On an MI355X: the attention step of bsmr_torch.SparseOperator through its composed path (sddmm -> softmax -> spmm) and
-its fused path (sddmm -> softmax_spmm, bsmr_sparse_attention), on the four shapes of tools/backward_lab.py, b = 1 and 8,
-fp32 and fp16 operands.  Per (shape, b, dtype):
-  fwd   the part that differs, on given scores P: softmax + spmm (raw calls) against the fused call;
-  step  the whole step, forward + backward through autograd: attention(Q, Kt, V, fused=False / True).
+"""On an MI355X: the attention step of bsmr_torch.SparseOperator through its composed path (sddmm -> softmax -> spmm),
+its fused path (sddmm -> softmax_spmm, bsmr_sparse_attention) and, for 16-bit operands, its one-pass path
+(bsmr_sparse_attention_qkv_16), on the four shapes of tools/backward_lab.py, b = 1 and 8, fp32, fp16 and bf16 operands.
+Per (shape, b, dtype):
+  fwd     the part in which composed and fused differ, on given scores P: softmax + spmm (raw calls) against the fused call;
+  fwdqkv  (16-bit) the whole forward from Q, Kt, V: sddmm + softmax + spmm, sddmm + fused call, the one-pass call;
+  step    the whole step, forward + backward through autograd: attention(Q, Kt, V, fused= / one_pass=).
+p_bytes is the size of the score array per batch (4 nnz): the one-pass forward neither writes nor reads it.
 Microseconds per call, event timing: 3 windows of 20 calls after 5 warm-up calls; every figure is [best, worst] of its
 three windows, so that a difference can be read against the windows' own spread.  The composed path runs first, both in
 the same process.  `agree` is max |O_fused - O_composed| / max |O|.
@@ -56,13 +59,13 @@ def main(names, out):
         lens = np.diff(ro.astype(np.int64))
         Kw = min(K, 128)
         line = {"shape": name, "M": rows, "N": cols, "nnz": int(ci.size), "K": Kw, "max_row": int(lens.max()),
-                "rows_over_chunk": int((lens > 512).sum())}
+                "rows_over_chunk": int((lens > 512).sum()), "p_bytes": 4 * int(ci.size)}
         op = bsmr_torch.SparseOperator(eng.CSR.from_arrays(rows, cols, ro, ci), device=0)   # the default modes
         scale = Kw ** -0.5
         us = {}
         for b in (1, 8):
             eng.sparse_attention_reserve(op._bw, Kw, b)
-            for dtype, tag in ((torch.float32, "f32"), (torch.float16, "f16")):
+            for dtype, tag in ((torch.float32, "f32"), (torch.float16, "f16"), (torch.bfloat16, "bf16")):
                 g = torch.Generator(device=dev).manual_seed(7)
                 leaf = lambda n: torch.randn(b, n, Kw, device=dev, generator=g).to(dtype).requires_grad_(True)
                 Q, Kt, V = leaf(rows), leaf(cols), leaf(cols)
@@ -70,8 +73,8 @@ def main(names, out):
                 P = op._sddmm(Q.detach(), Kt.detach())
                 Vd = V.detach()
 
-                def step(fused):
-                    op.attention(Q, Kt, V, fused=fused).backward(H)
+                def step(fused, one_pass=False):
+                    op.attention(Q, Kt, V, fused=fused, one_pass=one_pass).backward(H)
                     Q.grad = Kt.grad = V.grad = None
 
                 key = f"b{b}_{tag}"
@@ -82,6 +85,15 @@ def main(names, out):
                 Oc = op._spmm(op._softmax(P, scale), Vd, False).float()
                 Of = op._attention(P, Vd, scale)[0].float()
                 line[f"agree_{key}"] = float((Of - Oc).abs().max() / Oc.abs().max())
+                if dtype != torch.float32:   # the one-pass path beside the other two, from Q, Kt, V
+                    Qd, Ktd = Q.detach(), Kt.detach()
+                    us[f"fwdqkv_composed_{key}"] = windows(lambda: op._spmm(op._softmax(op._sddmm(Qd, Ktd), scale), Vd, False))
+                    us[f"fwdqkv_fused_{key}"] = windows(lambda: op._attention(op._sddmm(Qd, Ktd), Vd, scale))
+                    us[f"fwdqkv_one_pass_{key}"] = windows(lambda: op._attention_qkv(Qd, Ktd, Vd, scale))
+                    us[f"step_one_pass_{key}"] = windows(lambda: step(False, True))
+                    O1 = op._attention_qkv(Qd, Ktd, Vd, scale)[0].float()
+                    line[f"agree_one_pass_{key}"] = float((O1 - Oc).abs().max() / Oc.abs().max())
+                    del Qd, Ktd, O1
                 del Q, Kt, V, H, P, Vd, Oc, Of
         line["us"] = us
         text = json.dumps(line)
