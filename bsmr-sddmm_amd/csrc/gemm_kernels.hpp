@@ -62,14 +62,16 @@ constexpr size_t gemmLdsBytes(int PM, int NB) { return gemmRingBytes(PM, NB) + (
 
 #if defined(BSMR_GEMM_LAB)
 // labSkip: bit 0 MFMAs, 1 fragment reads (denseGemmCvt: the rounding step), 2 DMAs, 3 slab writes, 4 entry loads, 5 stores,
-// 6 denseGemmCvt's fragment reads.  labStamps (may be null): per (workgroup, wave) ten readings of the 100 MHz clock -
+// 6 denseGemmCvt's fragment reads.  labStamps (may be null): per (workgroup, wave) eleven readings of the 100 MHz clock -
 // 0 entry, 1 first stage requested, 2 own share of it landed, 3 first barrier passed, 4 K loop left, 5 + q pass q done;
-// denseGemmCvt: 8 = ticks the wave stood at the K loop's waits for its operands (summed over the slices), 9 = ticks from
+// denseGemmCvt: 8 = ticks the wave stood at the K loop's wait in front of the last row tile (summed over the slices), 9 = ticks from
 // the end of that wait to the slice's barrier passed (rounding, re-issue, barrier; summed).
-constexpr uint32_t kGemmLabStamps = 10;
+// 10 = ticks it stood at the wait in the middle of a slice, where one set of registers takes turns (summed).  Bit 2 leaves
+// out denseGemmCvt's register loads of both operands.
+constexpr uint32_t kGemmLabStamps = 11;
 #define GEMM_LAB_ARG , uint32_t labSkip, unsigned long long* labStamps
 #define GEMM_LAB_SKIP(bit) (labSkip & (1u << (bit)))
-#define GEMM_LAB_STAMPS unsigned long long labStamp[kGemmLabStamps] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, labSpan = 0
+#define GEMM_LAB_STAMPS unsigned long long labStamp[kGemmLabStamps] = {}, labSpan = 0
 #define GEMM_LAB_STAMP(i) labStamp[i] = __builtin_amdgcn_s_memrealtime()
 #define GEMM_LAB_SPAN_BEGIN labSpan = __builtin_amdgcn_s_memrealtime()
 #define GEMM_LAB_SPAN_END(i) labStamp[i] += __builtin_amdgcn_s_memrealtime() - labSpan
@@ -432,36 +434,39 @@ denseGemm(const void* __restrict__ Aop, const void* __restrict__ Bop, uint32_t a
 // the two waves of a column quarter the same columns of B - 2.9 times the casts the operands need, all of them in front of
 // the MFMAs of an in-order wave (measured, nips-like K = 128: 13.4 us against 9.1 us for the kernel on 16-bit copies).  Here
 // a slice of 32 k is rounded once, by the wave that requested it, into a 16-bit LDS image:
-//   A  a wave's PM / 4 chunks of 8 rows x 128 bytes come into REGISTERS (buffer loads through the resource that bounds
-//      them as it bounded the DMAs: 4 registers per chunk, lane l = piece l & 7 of row l >> 3) and are rounded from there;
-//   F  B's fp32 image, TWO stages of TN rows x 128 bytes, filled by LDS-DMA, lane-linear (piece = slot: nothing reads it
-//      by fragment).  A wave's share of F is PRIVATE to it: the wave that issued the DMAs of a 1-KiB chunk is the one
-//      that rounds it, so its own counted wait orders everything and no barrier guards F;
+//   A, B  a wave's PM / 4 chunks of A and NB / 4 chunks of B, 8 rows x 128 bytes each, come into REGISTERS (buffer loads
+//      through the resources that bound them as they bounded the DMAs of denseGemm: 4 registers per chunk, lane l = piece
+//      l & 7 of row l >> 3) and are rounded from there.  No fp32 image passes the LDS;
 //   H  two stages of (TM + TN) rows x 64 bytes of fp16 / bf16 (rows of 32 k), written by the rounding step - 64 lanes take
-//      1 KiB of a slice (registers or F, read linearly), round with the casts of convertOperands, write 8 bytes each - and
-//      read as MFMA fragments (ds_read_b128 of piece g of row r at slot g ^ swzH(r): conflict-free for the 16-lane groups
-//      a read is served in, as are the 8-byte writes).
-// Requests run two slices ahead.  vmcnt is ONE in-order counter, so the order of issue is part of the design: at the end
-// of slice t a wave requests A(t + 2), THEN B(t + 3); behind the MFMAs of slice t + 1 it waits with vmcnt(NB / 4) - A(t + 2)
-// and everything older, B(t + 2) with it, have landed, the DMAs of B(t + 3) stay outstanding - rounds both into
-// H[t & 1] and re-issues.  (A second fp32 stage for A too does not fit: 2 x 72 + 72 KiB at 256 x 320.)  ONE barrier per
-// slice publishes H[(t + 1) & 1]; everybody's reads of it, two slices ago, ended before the barrier in between.  Same
-// casts, same MFMA, same order of k steps: bit-identical to the conversion pass + 16-bit kernels.
+//      1 KiB of a slice from their registers, round with the casts of convertOperands, write 8 bytes each - and read as
+//      MFMA fragments (ds_read_b128 of piece g of row r at slot g ^ swzH(r): conflict-free for the 16-lane groups a read
+//      is served in, as are the 8-byte writes).
+// H[(t + 1) & 1] is free for all of slice t - everybody's reads of it ended before the barrier that closed slice t - 1 - so
+// a wave may round into it anywhere in slice t, and ONE barrier per slice publishes it.  Where the registers allow it
+// (at most 8 x 4 tiles per wave) A and B have a set of registers each: both are requested at the end of slice t - 1 and
+// waited for (vmcnt(0)) in front of the last row tile of slice t, whose MFMAs run beside the rounding.  The 8 x 5 tile
+// blocks have room for ONE set of NB / 4 chunks, which takes turns: it holds A(t + 1), requested at the end of slice
+// t - 1; in front of row tile m / 2 - 1 of slice t that is waited for, rounded beside that tile's MFMAs, and the set is
+// requested again as B(t + 1); in front of the last row tile that is waited for and rounded, and the set is requested as
+// A(t + 2).  Either way nothing is outstanding at a wait but the set it is for (and, in the last slice, the entry
+// words): the last wait of the loop is vmcnt(0) and the epilogue takes an LDS nothing is on its way to.  Same casts, same
+// MFMA, same order of k steps: bit-identical to the conversion pass + 16-bit kernels.
 constexpr uint32_t kGemmHalfRowBytes = 64u;                        // a row of an H stage: 32 k of 16 bits
 __host__ __device__ constexpr uint32_t gemmSwzH(uint32_t row) { return (4u - ((row >> 2) & 3u)) & 3u; }   // 0, 3, 2, 1
-// two fp32 stages of B, two 16-bit stages of both operands; reused as the eight waves' slabs by the epilogue
+// two 16-bit stages of both operands, but no less than the eight waves' slabs the epilogue reuses them as
 constexpr uint32_t gemmCvtRingBytes(int PM, int NB) {
-    const uint32_t used = 2u * (uint32_t)NB * 16u * kGemmRowBytes + 2u * (uint32_t)(PM + NB) * 16u * kGemmHalfRowBytes;
+    const uint32_t used = 2u * (uint32_t)(PM + NB) * 16u * kGemmHalfRowBytes;
     return used > kGemmWaves * kGemmSlabBytes ? used : kGemmWaves * kGemmSlabBytes;
 }
 constexpr size_t gemmCvtLdsBytes(int PM, int NB) { return gemmCvtRingBytes(PM, NB) + (size_t)PM * 16u * 4u; }
-static_assert(gemmCvtLdsBytes(16, 20) <= 160u * 1024u && gemmCvtLdsBytes(16, 16) <= 160u * 1024u && gemmCvtLdsBytes(8, 20) <= 160u * 1024u &&
-              gemmCvtLdsBytes(8, 16) <= 160u * 1024u, "the fp32 kernel's LDS fits a CU's 160 KiB");
+static_assert(gemmCvtLdsBytes(16, 20) <= 160u * 1024u, "the fp32 kernel's LDS fits a CU's 160 KiB");
 
-// A wave's chunks of an A slice into registers: the addresses (voff, kOff) and the bounds (the buffer resource over the
-// caller's aBytes: a piece that does not lie inside reads as zero) of the LDS-DMA form, gemmStagePart.
-template <uint32_t CHUNKS>
-__device__ __forceinline__ void gemmLoadChunks(const uint8_t* src, uint32_t srcBytes, const uint32_t* voff, uint32_t kOff, f32x4 (&v)[CHUNKS]) {
+// A wave's chunks of an operand's slice into registers (the first CHUNKS of a set of SET): the addresses (voff, kOff) and
+// the bounds (the buffer resource over the caller's srcBytes: a piece that does not lie inside reads as zero) of the
+// LDS-DMA form, gemmStagePart.
+template <uint32_t CHUNKS, uint32_t SET>
+__device__ __forceinline__ void gemmLoadChunks(const uint8_t* src, uint32_t srcBytes, const uint32_t* voff, uint32_t kOff, f32x4 (&v)[SET]) {
+    static_assert(CHUNKS <= SET, "the set holds the chunks");
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), 0, srcBytes, 0x00020000);
 #pragma unroll
     for (uint32_t j = 0; j < CHUNKS; ++j) v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[j], kOff, 0));
@@ -506,11 +511,16 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
              uint32_t gridG, uint32_t gridS, uint32_t fullGrid, Batch batch GEMM_LAB_ARG) {
     constexpr uint32_t K = 32u * KT, TM = PM * 16u, TN = NB * 16u, ROWS = TM + TN;
     constexpr uint32_t m = PM / kGemmWavesM, n = NB / kGemmWavesN, Q = (m * n + kGemmPassTiles - 1u) / kGemmPassTiles, L = kGemmWaves * Q;
-    constexpr uint32_t ADMAS = PM / 4u, BDMAS = NB / 4u;   // 1-KiB chunks of a slice per wave, 8 rows each: A's (registers), B's (F)
-    constexpr uint32_t fBytes = TN * kGemmRowBytes, hBytes = ROWS * kGemmHalfRowBytes, bAtH = TM * kGemmHalfRowBytes;
-    constexpr uint32_t hAt = 2u * fBytes, rowTableAt = gemmCvtRingBytes(PM, NB);
-    static_assert(hAt + 2u * hBytes <= rowTableAt, "F's two stages and H's two lie in front of the row table");
+    constexpr uint32_t ADMAS = PM / 4u, BDMAS = NB / 4u;   // 1-KiB chunks of a slice per wave, 8 rows each
+    constexpr uint32_t hBytes = ROWS * kGemmHalfRowBytes, bAtH = TM * kGemmHalfRowBytes;
+    constexpr uint32_t rowTableAt = gemmCvtRingBytes(PM, NB);
+    static_assert(2u * hBytes <= rowTableAt, "H's two stages lie in front of the row table");
     constexpr uint32_t kGemmWordChunk = m * n > 32u ? 4u : 8u;
+    // one set of registers for A's and B's chunks in turn where 8 x 5 tiles of accumulators leave no room for two (header);
+    // the row tile in front of which the turn's first half, A's, is waited for
+    constexpr bool kTurns = m * n > 32u;
+    constexpr uint32_t SET = kTurns && BDMAS > ADMAS ? BDMAS : ADMAS, kTurnTile = m / 2u - 1u;
+    static_assert(!kTurns || kTurnTile + 1u < m - 1u, "B's turn is requested in front of a row tile before the last one");
 
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t itemId = xcdContiguous(blockIdx.x, gridDim.x);
@@ -547,50 +557,50 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
     // (the row table's words are asked for in front of the operands: whoever uses them then waits for nothing younger)
     uint32_t myRowStart = 0;
     if (threadIdx.x < TM) myRowStart = rowStart[(size_t)itemId * TM + threadIdx.x];
-    // The requests of a slice, A's THEN B's (header): the fences keep hipcc's scheduler from moving the DMAs in front of the
-    // register loads, after which its own wait for the registers would be a wait for the youngest DMAs too.
-    f32x4 aNext[ADMAS];
+    // The requests of a slice.  `set` holds A's chunks (kTurns: A's and B's in turn, header), `bSet` B's (kTurns: those of
+    // slice 0 only, which are requested beside A's while the accumulators are not live yet, so that the first stage costs
+    // one round trip, not two).  The fences keep hipcc's scheduler from moving a request over the rounding of what its
+    // registers held, or anything over a wait.
+    f32x4 set[SET], bSet[BDMAS];
 #pragma unroll
-    for (uint32_t j = 0; j < ADMAS; ++j) aNext[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (uint32_t j = 0; j < SET; ++j) set[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (uint32_t j = 0; j < BDMAS; ++j) bSet[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto requestA = [&](uint32_t slice) {
         __builtin_amdgcn_sched_barrier(0);
-        if (slice < (uint32_t)KT && !GEMM_LAB_SKIP(2)) gemmLoadChunks<ADMAS>(Ab, aBytes, voffA, slice * kGemmRowBytes, aNext);
+        if (slice < (uint32_t)KT && !GEMM_LAB_SKIP(2)) gemmLoadChunks<ADMAS>(Ab, aBytes, voffA, slice * kGemmRowBytes, set);
         __builtin_amdgcn_sched_barrier(0);
     };
-    auto requestB = [&](uint32_t slice) {   // into F's stage slice & 1
+    auto requestB = [&](uint32_t slice, auto& into) {
         __builtin_amdgcn_sched_barrier(0);
-        if (slice < (uint32_t)KT && !GEMM_LAB_SKIP(2)) gemmStagePart<BDMAS>(Bb, bBytes, lds + (slice & 1u) * fBytes, wave, voffB, slice * kGemmRowBytes);
+        if (slice < (uint32_t)KT && !GEMM_LAB_SKIP(2)) gemmLoadChunks<BDMAS>(Bb, bBytes, voffB, slice * kGemmRowBytes, into);
         __builtin_amdgcn_sched_barrier(0);
     };
     requestA(0u);
-    requestB(0u);
+    requestB(0u, bSet);
     GEMM_LAB_STAMP(1);
     uint32_t myList[Q + 1];
 #pragma unroll
     for (uint32_t q = 0; q <= Q; ++q) myList[q] = lists[listBase + wave * Q + q];
 
-    // rounding step: my chunks of a slice -> stage `to` of H.  B's reads of F are issued together, A's registers are rounded
-    // while they are on their way, then B's: written chunk by chunk (read, round, write, read ...) every read waited for the
-    // write in front of it - the compiler cannot know that F and H do not overlap.
-    // (addresses: a chunk's place in F is one register plus j KiB + the stage; its rows' places in H are two registers per
-    // operand - the swizzle of row 8 c + (lane >> 3) depends on c's parity only - plus j * 512 + the stage)
-    const uint32_t fOfB = wave * BDMAS * 1024u + lane * 16u;
+    // rounding step: my chunks of a slice, in registers -> stage slice & 1 of H.
+    // (addresses: the places of a chunk's rows in H are two registers per operand - the swizzle of row 8 c + (lane >> 3)
+    // depends on c's parity only - plus j * 512 + the stage)
     auto hOf = [&](uint32_t part, uint32_t firstChunk, uint32_t odd) {
         const uint32_t quarter = (2u * (firstChunk + odd) + (lane >> 5)) & 3u;            // (row >> 2) & 3 of the lane's row
-        return hAt + part + firstChunk * 512u + (lane >> 3) * kGemmHalfRowBytes + (((piece >> 1) ^ ((4u - quarter) & 3u)) << 4) + ((piece & 1u) << 3);
+        return part + firstChunk * 512u + (lane >> 3) * kGemmHalfRowBytes + (((piece >> 1) ^ ((4u - quarter) & 3u)) << 4) + ((piece & 1u) << 3);
     };
     const uint32_t hOfA[2] = {hOf(0u, wave * ADMAS, 0u), hOf(0u, wave * ADMAS, 1u)};
     const uint32_t hOfB[2] = {hOf(bAtH, wave * BDMAS, 0u), hOf(bAtH, wave * BDMAS, 1u)};
-    auto roundChunks = [&](uint32_t slice) {
+    auto roundA = [&](uint32_t slice) {
         if (GEMM_LAB_SKIP(1)) return;
-        const uint32_t to = (slice & 1u) * hBytes;
-        f32x4 v[BDMAS];
 #pragma unroll
-        for (uint32_t j = 0; j < BDMAS; ++j) v[j] = *reinterpret_cast<const f32x4*>(lds + (slice & 1u) * fBytes + fOfB + j * 1024u);
+        for (uint32_t j = 0; j < ADMAS; ++j) gemmRoundPiece<MODE>(set[j], lds + hOfA[j & 1u] + j * 512u + (slice & 1u) * hBytes);
+    };
+    auto roundB = [&](uint32_t slice, const auto& from) {
+        if (GEMM_LAB_SKIP(1)) return;
 #pragma unroll
-        for (uint32_t j = 0; j < ADMAS; ++j) gemmRoundPiece<MODE>(aNext[j], lds + hOfA[j & 1u] + j * 512u + to);
-#pragma unroll
-        for (uint32_t j = 0; j < BDMAS; ++j) gemmRoundPiece<MODE>(v[j], lds + hOfB[j & 1u] + j * 512u + to);
+        for (uint32_t j = 0; j < BDMAS; ++j) gemmRoundPiece<MODE>(from[j], lds + hOfB[j & 1u] + j * 512u + (slice & 1u) * hBytes);
     };
 
     // fragment addresses in an H stage: piece g of row / column r at slot g ^ swzH(r)
@@ -618,16 +628,17 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
     if (kEarlyWords) firstWords();
 #endif
 
-    // slice 0: B(1) requested behind the entry words, so that the wait below leaves nothing but B(1) outstanding; A(0) and
-    // B(0) landed (my chunks), rounded into H[0]; A(1), then B(2) requested; H[0] published
-    requestB(1u);
-    if (KT > 1) gemmWaitRequests<BDMAS>(aNext); else gemmWaitRequests<0>(aNext);
+    // slice 0: A(0) and B(0) landed (my chunks; the entry words, requested behind them, too), rounded into H[0]; A(1) - with two
+    // sets B(1) too - requested; H[0] published
+    gemmWaitRequests<0>(set);
+    gemmWaitRequests<0>(bSet);
     GEMM_LAB_STAMP(2);
     if (threadIdx.x < TM) reinterpret_cast<uint32_t*>(lds + rowTableAt)[threadIdx.x] = myRowStart;   // (read behind the K loop's barriers)
-    roundChunks(0u);
+    roundA(0u);
+    roundB(0u, bSet);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     requestA(1u);
-    requestB(2u);
+    if (!kTurns) requestB(1u, bSet);
     __builtin_amdgcn_s_barrier();
     GEMM_LAB_STAMP(3);
 #if defined(BSMR_GEMM_LATE_WORDS)
@@ -640,24 +651,39 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
             firstWords();
             __builtin_amdgcn_sched_barrier(0);
         }
-        const uint8_t* base = lds + hAt + (t & 1u) * hBytes;
+        const uint8_t* base = lds + (t & 1u) * hBytes;
         u32x4 bf[n];
 #pragma unroll
         for (uint32_t j = 0; j < n; ++j)
             bf[j] = GEMM_LAB_SKIP(6) ? u32x4{lane, t, j, 0u} : *reinterpret_cast<const u32x4*>(base + bRead + j * 16u * kGemmHalfRowBytes);
 #pragma unroll
         for (uint32_t i = 0; i < m; ++i) {
-            if (i + 1u == m && t + 1u < (uint32_t)KT) {
-                // my chunks of slice t + 1 have landed - A(t + 1) and, requested before it, B(t + 1); B(t + 2)'s DMAs stay
-                // outstanding.  The last wait of the loop is vmcnt(0): nothing is on its way when the epilogue takes the
-                // LDS.  (MFMAs are register-only: without the fence hipcc moves the wait, and its own waits for A's
-                // registers, in front of the slice's MFMAs - the wave then stands there with nothing issued.  The last
-                // row tile's MFMAs stay behind the wait and run beside the rounding.)
-                __builtin_amdgcn_sched_barrier(0);
-                GEMM_LAB_SPAN_BEGIN;
-                if (t + 2u < (uint32_t)KT) gemmWaitRequests<BDMAS>(aNext); else gemmWaitRequests<0>(aNext);
-                GEMM_LAB_SPAN_END(8);
-                GEMM_LAB_SPAN_BEGIN;
+            if (t + 1u < (uint32_t)KT) {
+                // (MFMAs are register-only: without the fences hipcc moves a wait, and its own waits for the registers, in
+                // front of the slice's MFMAs - the wave then stands there with nothing issued.  The MFMAs of the row tile
+                // behind a wait run beside the rounding.)
+                if constexpr (kTurns) {
+                    if (i == kTurnTile) {   // the set's first turn: A(t + 1) has landed ...
+                        __builtin_amdgcn_sched_barrier(0);
+                        GEMM_LAB_SPAN_BEGIN;
+                        gemmWaitRequests<0>(set);
+                        GEMM_LAB_SPAN_END(10);
+                    }
+                    if (i == kTurnTile + 1u) {   // ... is rounded into the other stage of H, and the set takes B(t + 1)
+                        roundA(t + 1u);
+                        requestB(t + 1u, set);
+                    }
+                }
+                if (i + 1u == m) {
+                    // my chunks of slice t + 1 have landed - the set's second turn, B(t + 1), or both sets.  Nothing else is
+                    // outstanding: the last wait of the loop finds nothing on its way when the epilogue takes the LDS.
+                    __builtin_amdgcn_sched_barrier(0);
+                    GEMM_LAB_SPAN_BEGIN;
+                    gemmWaitRequests<0>(set);
+                    if (!kTurns) gemmWaitRequests<0>(bSet);
+                    GEMM_LAB_SPAN_END(8);
+                    GEMM_LAB_SPAN_BEGIN;
+                }
             }
             const u32x4 af = GEMM_LAB_SKIP(6) ? u32x4{lane, t, i, 2u} : *reinterpret_cast<const u32x4*>(base + aRead + i * 16u * kGemmHalfRowBytes);
             if (!GEMM_LAB_SKIP(0)) {
@@ -670,12 +696,16 @@ denseGemmCvt(const float* __restrict__ Aop, const float* __restrict__ Bop, uint3
             }
         }
         if (t + 1u < (uint32_t)KT) {
-            // round them into the other stage of H, then the registers take A(t + 2) and the stage of F just read (this
-            // wave's own reads of it are over: lgkmcnt(0)) takes B(t + 3)
-            roundChunks(t + 1u);
+            // round them into the other stage of H, then the registers take slice t + 2 (kTurns: A's chunks of it)
+            if constexpr (kTurns) {
+                roundB(t + 1u, set);
+            } else {
+                roundA(t + 1u);
+                roundB(t + 1u, bSet);
+            }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             requestA(t + 2u);
-            requestB(t + 3u);
+            if (!kTurns) requestB(t + 2u, bSet);
         } else {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             GEMM_LAB_SPAN_BEGIN;

@@ -40,7 +40,7 @@ struct Variant {
     int KT, PM, NB, mode;
     bool src32;
     Kernel kernel;
-    bool shared = false;   // denseGemmCvt: one rounding per element (A from registers, B from an fp32 LDS image) into a 16-bit LDS image
+    bool shared = false;   // denseGemmCvt: one rounding per element, from registers into a 16-bit LDS image
 };
 #define V(name, KT, PM, NB, MODE) {name, KT, PM, NB, MODE, false, bsmr::denseGemm<KT, PM, NB, MODE, false>}
 #define V32(name, KT, PM, NB, MODE) {name, KT, PM, NB, MODE, true, bsmr::denseGemm<KT, PM, NB, MODE, true>}
@@ -242,15 +242,16 @@ int main(int argc, char** argv) {
             if (seen) printf("    %-22s %6.2f %6.2f %6.2f\n", kNames[i], lo, sum / seen, hi);
         }
         {   // the K loop per slice: first barrier passed -> loop left, and denseGemmCvt's two spans inside it (means over the waves)
-            double loop = 0, wait = 0, rest = 0;
+            double loop = 0, wait = 0, rest = 0, mid = 0;
             for (size_t w = 0; w < count / NS; ++w) {
                 loop += (double)(st[w * NS + 4] - st[w * NS + 3]) * 0.01;
                 wait += (double)st[w * NS + 8] * 0.01;
                 rest += (double)st[w * NS + 9] * 0.01;
+                mid += (double)st[w * NS + 10] * 0.01;
             }
             const double per = 1.0 / ((double)(count / NS) * v->KT);
-            printf("    per slice (%d slices): period %.3f us, at the operand wait %.3f us, wait's end -> barrier passed %.3f us\n", v->KT,
-                   loop * per, wait * per, rest * per);
+            printf("    per slice (%d slices): period %.3f us, at the operand wait %.3f us, at the mid-slice wait %.3f us, wait's end -> barrier passed %.3f us\n",
+                   v->KT, loop * per, wait * per, mid * per, rest * per);
         }
         // the workgroups' last readings, sorted: how the launch drains
         std::vector<double> ends;
