@@ -10,3 +10,13 @@ hipError_t bsmrLaunchAttnQkv(const void* items, uint32_t numItems, const void* s
                              float scale, const uint16_t* Q, const uint16_t* Kt, const uint16_t* V, uint16_t* O, float* m,
                              float* s, float* partial, float* sPart, float* mPart, uint32_t K, uint32_t Kv, uint32_t M,
                              uint32_t N, uint32_t numSlots, uint32_t numBatches, bool bf16, hipStream_t stream);
+
+// The one entry of csrc/attention_qkv_kv.hip: the same for attnQkvKv (csrc/attention_qkv_kv_kernels.hpp) and that unit's
+// attnQkvMerge.  Kt / V: the codes as the cache holds them; kvFormat: their format (the fp8 values are BSMR_FP8_E4M3 /
+// _E5M2); mx: Ks / Vs are the E8M0 block scales (always with e2m1), otherwise they are not read.
+enum : int { kQkvKvE4M3 = 0, kQkvKvE5M2 = 1, kQkvKvE2M1 = 2 };
+hipError_t bsmrLaunchAttnQkvKv(const void* items, uint32_t numItems, const void* splits, uint32_t numSplits, const uint32_t* src,
+                               float scale, const uint16_t* Q, const uint8_t* Kt, const uint8_t* Ks, const uint8_t* V,
+                               const uint8_t* Vs, uint16_t* O, float* m, float* s, float* partial, float* sPart, float* mPart,
+                               uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots, uint32_t numBatches, bool bf16,
+                               int kvFormat, bool mx, hipStream_t stream);

@@ -257,6 +257,12 @@ HIP_SYMBOLS = {
     "bsmr_sparse_attention_qkv_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bsmr_sparse_attention_qkv_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
                                      [C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_kv8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
+                                      [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_kv8_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
+                                         [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_kv4_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
+                                         [C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_widen_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
     "bsmr_sddmm_b8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
                                 C.c_void_p]),
@@ -939,6 +945,34 @@ def sparse_attention_qkv_16(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt_pt
     _check(hip().bsmr_sparse_attention_qkv_16(bw, K, Kv, scale, Q_ptr or None, Kt_ptr or None, V_ptr or None, O_ptr or None,
                                               m_ptr or None, s_ptr or None, num_batches, mode, stream),
            "bsmr_sparse_attention_qkv_16")
+
+
+# --- one-pass sparse attention on a quantised KV cache: Kt and V as fp8 bytes or e2m1 nibbles, with or without MX block
+# scales, widened in registers (include/bsmr_hip.h "One-pass sparse attention on fp8, MXFP8 and MXFP4 keys and values") ---
+def sparse_attention_qkv_kv8(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt8_ptr: int, V8_ptr: int, O_ptr: int, m_ptr: int,
+                             s_ptr: int, num_batches: int = 1, stream: int = 0, mode=COMPUTE_F16, fmt=FP8_E4M3):
+    """sparse_attention_qkv_16(Q, widen(Kt8), widen(V8)) bit for bit, the fp8 bytes read in place; fmt FP8_E4M3 / FP8_E5M2"""
+    _check(hip().bsmr_sparse_attention_qkv_kv8(bw, K, Kv, scale, Q_ptr or None, Kt8_ptr or None, V8_ptr or None, O_ptr or None,
+                                               m_ptr or None, s_ptr or None, num_batches, mode, fmt, stream),
+           "bsmr_sparse_attention_qkv_kv8")
+
+
+def sparse_attention_qkv_kv8_mx(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt8_ptr: int, Kts_ptr: int, V8_ptr: int,
+                                Vs_ptr: int, O_ptr: int, m_ptr: int, s_ptr: int, num_batches: int = 1, stream: int = 0,
+                                mode=COMPUTE_F16, fmt=FP8_E4M3):
+    """the one-pass forward on dq(Kt8, Kts) and dq(V8, Vs): the scales [b][N][K/32] and [b][N][Kv/32] E8M0 bytes"""
+    _check(hip().bsmr_sparse_attention_qkv_kv8_mx(bw, K, Kv, scale, Q_ptr or None, Kt8_ptr or None, Kts_ptr or None,
+                                                  V8_ptr or None, Vs_ptr or None, O_ptr or None, m_ptr or None, s_ptr or None,
+                                                  num_batches, mode, fmt, stream), "bsmr_sparse_attention_qkv_kv8_mx")
+
+
+def sparse_attention_qkv_kv4_mx(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt4_ptr: int, Kts_ptr: int, V4_ptr: int,
+                                Vs_ptr: int, O_ptr: int, m_ptr: int, s_ptr: int, num_batches: int = 1, stream: int = 0,
+                                mode=COMPUTE_F16):
+    """the one-pass forward on dq(Kt4, Kts) and dq(V4, Vs): e2m1 codes, two per byte, the scales mandatory"""
+    _check(hip().bsmr_sparse_attention_qkv_kv4_mx(bw, K, Kv, scale, Q_ptr or None, Kt4_ptr or None, Kts_ptr or None,
+                                                  V4_ptr or None, Vs_ptr or None, O_ptr or None, m_ptr or None, s_ptr or None,
+                                                  num_batches, mode, stream), "bsmr_sparse_attention_qkv_kv4_mx")
 
 
 # --- fp8 keys and values: the column-side operand as OCP fp8 bytes (fmt FP8_E4M3 / FP8_E5M2), widened exactly to the

@@ -313,12 +313,18 @@ class SparseOperator:
         Kt and V may each be fp8 or fp4; out_dtype (default Q.dtype) is the result's dtype when V is, unused otherwise.
         Kt_scale / V_scale: the MX block scales of an fp8 Kt / V, independently of each other.
         one_pass=True: the same function in one kernel with an online softmax (bsmr_sparse_attention_qkv_16) - the scores
-        are never stored in the forward; Q, Kt, V fp16 or bf16 of one dtype, K and Kv at most 512, no scales, no out_dtype."""
+        are never stored in the forward; Q fp16 or bf16, K and Kv at most 512, no out_dtype (O has Q's dtype).  Kt and V are
+        both of Q's dtype (no scales), or both one fp8 dtype (Kt_scale and V_scale both given or both None), or both fp4
+        (both scales): the quantised forms read the cache bytes in place (bsmr_sparse_attention_qkv_kv8 / _kv8_mx /
+        _kv4_mx) and give a gradient to Q alone."""
         if one_pass:
             if fused:
                 raise ValueError("fused=True with one_pass=True: they are two different paths, choose one")
-            self._check_one_pass(Q, Kt, V, out_dtype, Kt_scale, V_scale)
-            return _AttentionOnePass.apply(self, Q, Kt, V, Q.shape[-1] ** -0.5 if scale is None else scale)
+            quantised, Kts, Vs = self._check_one_pass(Q, Kt, V, out_dtype, Kt_scale, V_scale)
+            scale = Q.shape[-1] ** -0.5 if scale is None else scale
+            if quantised:
+                return _AttentionOnePassKv.apply(self, Q, Kt, V, scale, Kts, Vs)
+            return _AttentionOnePass.apply(self, Q, Kt, V, scale)
         self._no_scale(None if _is8(Kt) or _is4(Kt) else Kt_scale, "Kt_scale", "Kt")   # both refused before any device work
         self._no_scale(None if _is8(V) or _is4(V) else V_scale, "V_scale", "V")
         if _is4(V):
@@ -610,23 +616,41 @@ class SparseOperator:
                              self._stream(), mode=_MODE16.get(X.dtype, eng.COMPUTE_F32))
         return O, m, s
 
-    @staticmethod
-    def _check_one_pass(Q, Kt, V, out_dtype, Kt_scale, V_scale):
-        """the limits of attention(one_pass=True), named before any device work"""
+    def _check_one_pass(self, Q, Kt, V, out_dtype, Kt_scale, V_scale):
+        """the limits of attention(one_pass=True), named before any device work: (quantised, Kt's scales, V's scales) -
+        whether Kt and V are fp8 or fp4, and their MX block scales as uint8 tensors or None"""
         for t, name in ((Q, "Q"), (Kt, "Kt"), (V, "V")):
             if not isinstance(t, torch.Tensor):
                 raise ValueError(f"{name}: expected a torch.Tensor")
-            if t.dtype not in _MODE16:
-                raise ValueError(f"{name}: dtype {t.dtype} - one_pass=True takes torch.float16 or torch.bfloat16 operands only "
-                                 "(fp32, fp8 and fp4 go through one_pass=False)")
-            if t.dtype != Q.dtype:
-                raise ValueError(f"{name}: dtype {t.dtype} beside Q's {Q.dtype} - one_pass=True needs one dtype for Q, Kt and V")
-            if t.dim() in (2, 3) and not 32 <= t.shape[-1] <= ONE_PASS_MAX_K:
-                raise ValueError(f"{name}: {t.shape[-1]} features - one_pass=True takes K and Kv in 32 ... {ONE_PASS_MAX_K}")
-        if Kt_scale is not None or V_scale is not None:
-            raise ValueError("Kt_scale / V_scale: one_pass=True takes no MX block scales (no fp8 or fp4 operands)")
+            if t.dim() in (2, 3) and not 32 <= _k_of(t) <= ONE_PASS_MAX_K:
+                raise ValueError(f"{name}: {_k_of(t)} features - one_pass=True takes K and Kv in 32 ... {ONE_PASS_MAX_K}")
         if out_dtype is not None:
             raise ValueError("out_dtype: one_pass=True gives Q's dtype and takes no out_dtype")
+        if Q.dtype not in _MODE16:
+            raise ValueError(f"Q: dtype {Q.dtype} - one_pass=True takes a torch.float16 or torch.bfloat16 Q (fp32 goes "
+                             "through one_pass=False)")
+        quantised = [_is8(t) or _is4(t) for t in (Kt, V)]
+        if any(quantised) and (not all(quantised) or Kt.dtype != V.dtype):
+            raise ValueError(f"Kt {Kt.dtype} beside V {V.dtype}: one_pass=True takes Kt and V in one format - both Q's dtype, "
+                             "both one fp8 dtype or both fp4; mixed formats go through one_pass=False")
+        if not any(quantised):
+            for t, name in ((Kt, "Kt"), (V, "V")):
+                if t.dtype not in _MODE16:
+                    raise ValueError(f"{name}: dtype {t.dtype} - one_pass=True takes torch.float16, torch.bfloat16, fp8 or fp4 "
+                                     "keys and values (fp32 goes through one_pass=False)")
+                if t.dtype != Q.dtype:
+                    raise ValueError(f"{name}: dtype {t.dtype} beside Q's {Q.dtype} - 16-bit Kt and V share Q's dtype")
+            if Kt_scale is not None or V_scale is not None:
+                raise ValueError("Kt_scale / V_scale: MX block scales belong to fp8 or fp4 keys and values, these are 16-bit")
+            return False, None, None
+        self._no_grad8(Kt, "Kt")
+        self._no_grad8(V, "V")
+        if _is8(Kt) and Kt_scale is None and V_scale is None:
+            return True, None, None
+        if _is8(Kt) and (Kt_scale is None or V_scale is None):
+            raise ValueError("Kt_scale / V_scale: one_pass=True takes fp8 keys and values both with MX block scales or both "
+                             "without; one scaled operand beside an unscaled one goes through one_pass=False")
+        return True, self._check_scale(Kt_scale, "Kt_scale", Kt), self._check_scale(V_scale, "V_scale", V)
 
     def _attention_qkv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale):
         """(O, m, s) of the one-pass forward; O (M, Kv) or (b, M, Kv) in Q's dtype, m and s (M,) or (b, M) fp32"""
@@ -646,6 +670,35 @@ class SparseOperator:
         s = torch.empty_like(m)
         eng.sparse_attention_qkv_16(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(),
                                     m.data_ptr(), s.data_ptr(), b or 1, self._stream(), mode=_MODE16[Q.dtype])
+        return O, m, s
+
+    def _attention_qkv_kv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, Kts=None, Vs=None):
+        """_attention_qkv on fp8 or fp4 Kt and V of one dtype; Kts / Vs: their MX block scales (uint8), both or neither"""
+        b, K = self._check(Q, "Q", self.M, None)
+        fp4 = _is4(Kt)
+        _, K2 = self._check4(Kt, "Kt", self.N, (b,)) if fp4 else self._check(Kt, "Kt", self.N, (b,), fp8=True)
+        _, Kv = self._check4(V, "V", self.N, (b,)) if fp4 else self._check(V, "V", self.N, (b,), fp8=True)
+        if K2 != K:
+            raise ValueError(f"Q and Kt disagree on K ({K} vs {K2})")
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"scale: {scale!r} is not a number") from None
+        if not math.isfinite(scale):
+            raise ValueError(f"scale: {scale} is not finite")
+        O = torch.empty((self.M, Kv) if b is None else (b, self.M, Kv), dtype=Q.dtype, device=self.device)
+        m = torch.empty((self.M,) if b is None else (b, self.M), dtype=torch.float32, device=self.device)
+        s = torch.empty_like(m)
+        out = (O.data_ptr(), m.data_ptr(), s.data_ptr(), b or 1, self._stream())
+        if fp4:
+            eng.sparse_attention_qkv_kv4_mx(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), Kts.data_ptr(), V.data_ptr(),
+                                            Vs.data_ptr(), *out, mode=_MODE16[Q.dtype])
+        elif Kts is not None:
+            eng.sparse_attention_qkv_kv8_mx(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), Kts.data_ptr(), V.data_ptr(),
+                                            Vs.data_ptr(), *out, mode=_MODE16[Q.dtype], fmt=_MODE8[Kt.dtype])
+        else:
+            eng.sparse_attention_qkv_kv8(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), *out,
+                                         mode=_MODE16[Q.dtype], fmt=_MODE8[Kt.dtype])
         return O, m, s
 
     def _attention_backward(self, v, m, s, dW, O, dO, scale):
@@ -889,6 +942,30 @@ class _AttentionOnePass(torch.autograd.Function):
         if need_q or need_k:
             dQ, dKt = op._sddmm_backward(dP, Q, Kt, need_q, need_k)
         return None, dQ, dKt, dV, None
+
+
+class _AttentionOnePassKv(torch.autograd.Function):
+    """attention(one_pass=True) on fp8 or fp4 Kt and V (Kts / Vs: their MX block scales or None): dQ alone, from calls the
+    engine already has - P and dO V^T by the quantised SDDMM, the fused backward, then dQ = S_dP dq(Kt) by the quantised SpMM"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, Q, Kt, V, scale, Kts, Vs):
+        O, m, s = op._attention_qkv_kv(Q, Kt, V, scale, Kts, Vs)
+        ctx.op, ctx.scale, ctx.Kts, ctx.Vs = op, float(scale), Kts, Vs
+        ctx.save_for_backward(Q, Kt, V, O, m, s)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        op = ctx.op
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None, None
+        Q, Kt, V, O, m, s = ctx.saved_tensors
+        dO = _grad(dO, O.dtype)
+        sddmm, spmm = (op._sddmm_b4, op._spmm_x4) if _is4(Kt) else (op._sddmm_b8, op._spmm_x8)
+        P = sddmm(Q, Kt, ctx.Kts)   # the scores exist only from here on
+        dP, _ = op._attention_backward(P, m, s, sddmm(dO, V, ctx.Vs), O, dO, ctx.scale)
+        return None, spmm(dP, Kt, Q.dtype, ctx.Kts), None, None, None, None, None
 
 
 class _SoftmaxSpMM8(torch.autograd.Function):

@@ -790,6 +790,53 @@ int bsmr_sparse_attention_qkv_16(bsmr_backward *bw, uint32_t K, uint32_t Kv, flo
                                  const void *Kt16_dev, const void *V16_dev, void *O16_dev, float *m_dev, float *s_dev,
                                  uint32_t num_batches, int compute_mode, void *stream);
 
+/* ---- One-pass sparse attention on fp8, MXFP8 and MXFP4 keys and values (revision 5, added without any layout change) ----
+ * bsmr_sparse_attention_qkv_16 with Kt and V as a quantised KV cache holds them, in the formats of "fp8 keys and values",
+ * "MX block scales" and "MXFP4 keys and values" below: the kernel reads the cache bytes and widens in registers.  No 16-bit
+ * copy of Kt is made and nothing of size nnz exists.  Q [b][M][K] and O [b][M][Kv] are fp16 or bf16 (compute_mode), m and
+ * s [b][M] fp32.  K and Kv are multiples of 32 in 32 ... 512.
+ *   _kv8      Kt8 [b][N][K] and V8 [b][N][Kv] bytes of one fp8_format (BSMR_FP8_E4M3 / BSMR_FP8_E5M2), no scales
+ *   _kv8_mx   the same with E8M0 block scales Kts [b][N][K/32] and Vs [b][N][Kv/32] (code e = 2^(e - 127), 255 = NaN)
+ *   _kv4_mx   Kt4 [b][N][K/2] and V4 [b][N][Kv/2] bytes of e2m1 codes (element 2i the low nibble of byte i) under
+ *             mandatory block scales of the same shapes
+ * Numerical contract: that of "One-pass sparse attention" with two substitutions.  widen(code) is the exact value of a
+ * code (every fp8 and e2m1 code is a value of fp16 and of bf16); sc = 2^(E - 127) as decoded above.
+ *   p_t   Element ownership is unchanged: lane j of 4 owns k = 32 i + 8 j ... 32 i + 8 j + 7, i ascending.
+ *         Without scales: ONE fp32 accumulator from +0 over all the lane's elements in ascending k, two per step
+ *         (v_dot2_f32_f16 / _bf16 on Q and widen(Kt), exact products), then (x0 + x1) + (x2 + x3).  So
+ *           bsmr_sparse_attention_qkv_kv8(Q, Kt8, V8) == bsmr_sparse_attention_qkv_16(Q, widen(Kt8), widen(V8))
+ *         in every bit of O, m and s.
+ *         With scales, for block i ascending: d_i = a fresh fp32 accumulator from +0 over the lane's 8 elements of the
+ *         block (four steps), then p = fmaf(d_i, sc_i, p) with sc_i the scale of block i of row c_t; then the same
+ *         (x0 + x1) + (x2 + x3).  The scale multiplies an fp32 partial dot, never a 16-bit value: nothing is narrowed.
+ *         At most 4 + K/32 + 2 roundings per term.
+ *   z_t = fl(scale p_t).  A scale code 255 or an fp8 NaN code in row c_t makes z_t NaN: the flag rule, that row of O NaN.
+ *   V     acc_k = fmaf(e_t, x, acc_k) with x = widen(V[c_t,k]) without scales and x = fl(widen(V[c_t,k]) sc) with them:
+ *         one IEEE fp32 multiplication, the element of bsmr_sparse_attention_x8_mx / _x4_mx.  s never sees the scales.
+ * Tiles, rescaling, chunks, the merge, the skip of a tile or chunk at m = -inf, the division and the one rounding of O,
+ * the exact cases and the reproducibility are those of bsmr_sparse_attention_qkv_16.  Every e2m1 value is an e4m3 value:
+ * a _kv4_mx call equals, bit for bit, the _kv8_mx call (BSMR_FP8_E4M3) on the re-encoded codes with the same scales.
+ * Forward bound: that of "One-pass sparse attention" against fp64 on Q and the dequantised dq(Kt), dq(V), with |Kt| and |V|
+ * read as |dq|, wherever the block-scale products neither overflow nor fall into the subnormal range.
+ * Workspace: that of bsmr_sparse_attention_qkv_16 - the partials are fp32 whatever the KV format - sized by
+ * bsmr_sparse_attention_qkv_reserve(K, Kv, num_batches).
+ * Checked before any device work, in this order: a NULL handle or a non-finite scale (BSMR_ERR_INVALID_ARG), K or Kv
+ * (BSMR_ERR_UNSUPPORTED_K), compute_mode and fp8_format, more than 65535 batches, then the pointers: 16 bytes for Q, Kt, V
+ * and O, 4 for m and s; the scales NULL only with nnz = 0, at any alignment.  num_batches = 0 is a no-op behind them.  With
+ * nnz = 0 the inputs may be NULL and the call writes O = +0, m = -inf, s = 0.  Every byte address and batch stride (N K,
+ * N K / 2, N K / 32 bytes) is formed in 64 bits. */
+int bsmr_sparse_attention_qkv_kv8(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                  const void *Kt8_dev, const void *V8_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                  uint32_t num_batches, int compute_mode, int fp8_format, void *stream);
+int bsmr_sparse_attention_qkv_kv8_mx(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                     const void *Kt8_dev, const void *Kt_scales_dev, const void *V8_dev,
+                                     const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                     uint32_t num_batches, int compute_mode, int fp8_format, void *stream);
+int bsmr_sparse_attention_qkv_kv4_mx(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                     const void *Kt4_dev, const void *Kt_scales_dev, const void *V4_dev,
+                                     const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                     uint32_t num_batches, int compute_mode, void *stream);
+
 /* ---- fp8 keys and values (revision 5, added without any layout change; no reference counterpart) ----
  * The column-side operand - B / Kt of the SDDMM, X / V of the SpMM and of the fused attention - may be OCP fp8, one byte per
  * element, as an fp8 KV cache holds it: fp8_format BSMR_FP8_E4M3 (e4m3fn: no infinity, two NaN codes) or BSMR_FP8_E5M2 (two

@@ -10,7 +10,11 @@ p_bytes is the size of the score array per batch (4 nnz): the one-pass forward n
 Microseconds per call, event timing: 3 windows of 20 calls after 5 warm-up calls; every figure is [best, worst] of its
 three windows, so that a difference can be read against the windows' own spread.  The composed path runs first, both in
 the same process.  `agree` is max |O_fused - O_composed| / max |O|.
-Usage: python tools/attention_lab.py [--out FILE] [shape ...]   (one JSON line per shape)"""
+--kv {fp8,mxfp8,mxfp4}: instead of the above, the forward on a quantised KV cache at K = Kv = 128, fp16 and bf16 Q: the
+fused path (quantised sddmm, which first writes a 16-bit copy of Kt and then P, + the quantised fused call) against the
+one-pass call on the same codes (bsmr_sparse_attention_qkv_kv8 / _kv8_mx / _kv4_mx), the fused path first.  kt16_bytes and
+p_bytes are what the one-pass forward neither allocates nor moves, per batch: the 16-bit copy of Kt and the scores.
+Usage: python tools/attention_lab.py [--kv FORMAT] [--out FILE] [shape ...]   (one JSON line per shape)"""
 import argparse
 import json
 import sys
@@ -105,12 +109,56 @@ def main(names, out):
         torch.cuda.empty_cache()
 
 
+def main_kv(names, out, kv):
+    fmt = getattr(torch, "float4_e2m1fn_x2", None) if kv == "mxfp4" else torch.float8_e4m3fn
+    for name in names:
+        gen, kwargs, _ = SHAPES[name]
+        rows, cols, ro, ci = getattr(synth, gen)(**kwargs)
+        ro = np.ascontiguousarray(ro, dtype=np.uint32)
+        ci = np.ascontiguousarray(ci, dtype=np.uint32)
+        Kw = 128
+        line = {"shape": name, "kv": kv, "M": rows, "N": cols, "nnz": int(ci.size), "K": Kw, "p_bytes": 4 * int(ci.size),
+                "kt16_bytes": 2 * cols * Kw, "kt_bytes": cols * Kw // (2 if kv == "mxfp4" else 1)}
+        op = bsmr_torch.SparseOperator(eng.CSR.from_arrays(rows, cols, ro, ci), device=0)
+        us = {}
+        for b in (1, 8):
+            g = torch.Generator(device=dev).manual_seed(7)
+            rand = lambda n: torch.randn(b, n, Kw, device=dev, generator=g)
+            quant = lambda: bsmr_torch.mx_quantize(rand(cols), fmt) if kv != "fp8" else (rand(cols).to(fmt),)
+            Kt, Kts = (quant() + (None,))[:2]
+            V, Vs = (quant() + (None,))[:2]
+            for dtype, tag in ((torch.float16, "f16"), (torch.bfloat16, "bf16")):
+                Q = rand(rows).to(dtype)
+                key = f"b{b}_{tag}"
+                fused = lambda: op.attention(Q, Kt, V, fused=True, Kt_scale=Kts, V_scale=Vs)
+                one = lambda: op.attention(Q, Kt, V, one_pass=True, Kt_scale=Kts, V_scale=Vs)
+                us[f"fwd_fused_{key}"] = windows(fused)
+                us[f"fwd_one_pass_{key}"] = windows(one)
+                Of = fused().float()
+                line[f"agree_one_pass_{key}"] = float((one().float() - Of).abs().max() / Of.abs().max())
+                del Q, Of
+            del Kt, Kts, V, Vs
+        line["us"] = us
+        text = json.dumps(line)
+        print(text, flush=True)
+        if out:
+            with open(out, "a") as f:
+                f.write(text + "\n")
+        del op
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kv", choices=("fp8", "mxfp8", "mxfp4"), default=None,
+                    help="time the forward on a quantised KV cache: fused path against one-pass")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("shapes", nargs="*", help=f"any of {', '.join(SHAPES)} (default: all)")
     args = ap.parse_args()
     unknown = [n for n in args.shapes if n not in SHAPES]
     if unknown:
         ap.error(f"unknown shape(s) {unknown}")
-    main(args.shapes or list(SHAPES), args.out)
+    if args.kv:
+        main_kv(args.shapes or list(SHAPES), args.out, args.kv)
+    else:
+        main(args.shapes or list(SHAPES), args.out)
