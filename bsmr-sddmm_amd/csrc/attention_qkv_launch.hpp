@@ -11,7 +11,29 @@ hipError_t bsmrLaunchAttnQkv(const void* items, uint32_t numItems, const void* s
                              float* s, float* partial, float* sPart, float* mPart, uint32_t K, uint32_t Kv, uint32_t M,
                              uint32_t N, uint32_t numSlots, uint32_t numBatches, bool bf16, hipStream_t stream);
 
-// The one entry of csrc/attention_qkv_kv.hip: the same for attnQkvKv (csrc/attention_qkv_kv_kernels.hpp) and that unit's
+// A row of a panel with blocks, as attnQkvBlkMerge (csrc/attention_qkv_blocked_kernels.hpp) merges it: its residue chunks
+// on the slots resFirst ... of attnQkv's partial area, then its block units on the rows blkFirst, blkFirst + 16, ... of
+// the block partial area (a unit owns 16 consecutive rows, one per row of its panel).
+struct BsmrAttnBlkRow {
+    uint32_t dest;       // the row of S
+    uint32_t resFirst;
+    uint32_t resCount;   // 0: the row has no residue entry
+    uint32_t blkFirst;
+    uint32_t blkCount;   // >= 1
+};
+
+// The one entry of csrc/attention_qkv_blocked.hip: attnQkvBlocks over the RPHM's blocks, then attnQkvBlkMerge.  units:
+// BlkSegment[numUnits] if `segments`, else BlkPanel[numUnits]; cells / cols / panelRows / zeros: the device format of
+// bsmr_backward_attach_blocks; rows: BsmrAttnBlkRow[numRows].  partial / sPart / mPart [b][numSlots]: what attnQkv left for
+// the residue chunks; bPart [b][16 numUnits][Kv], bs and bm [b][16 numUnits]: the block partials, written here.
+hipError_t bsmrLaunchAttnQkvBlocks(const void* units, uint32_t numUnits, bool segments, const uint32_t* panelRows,
+                                   const void* cells, const void* cols, const float* zeros, const BsmrAttnBlkRow* rows,
+                                   uint32_t numRows, float scale, const uint16_t* Q, const uint16_t* Kt, const uint16_t* V,
+                                   uint16_t* O, float* m, float* s, const float* partial, const float* sPart,
+                                   const float* mPart, uint32_t numSlots, float* bPart, float* bs, float* bm, uint32_t K,
+                                   uint32_t Kv, uint32_t M, uint32_t N, uint32_t numBatches, bool bf16, hipStream_t stream);
+
+// The one entry of csrc/attention_qkv_kv.hip: bsmrLaunchAttnQkv for attnQkvKv (csrc/attention_qkv_kv_kernels.hpp) and that unit's
 // attnQkvMerge.  Kt / V: the codes as the cache holds them; kvFormat: their format (the fp8 values are BSMR_FP8_E4M3 /
 // _E5M2); mx: Ks / Vs are the E8M0 block scales (always with e2m1), otherwise they are not read.
 enum : int { kQkvKvE4M3 = 0, kQkvKvE5M2 = 1, kQkvKvE2M1 = 2 };

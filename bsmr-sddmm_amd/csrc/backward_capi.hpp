@@ -13,6 +13,16 @@
 #include "spmm_blocked_kernels.hpp"   // (includes spmm_kernels.hpp)
 #include "fp8_kernels.hpp"            // the fp8 arms of runGather and runAttention (includes attention_kernels.hpp)
 #include "fp4_kernels.hpp"            // ... and the MXFP4 arms
+#include "attention_qkv_launch.hpp"   // BsmrAttnBlkRow
+
+// What bsmr_sparse_attention_qkv_blocked_16 adds to attached blocks (csrc/attention_qkv_blocked_capi.hpp), built by its
+// first call or reserve: the residue items of the rows of panels with blocks as attnQkv wants them - dest = the row of S,
+// every chunk on a partial slot (numbered behind the handle's own) - and one record per such row for the merge.
+struct BwAttnBlk {
+    DevArray<bsmr::BwItem> items;
+    DevArray<BsmrAttnBlkRow> rows;
+    uint32_t numItems = 0, numRows = 0, numSlots = 0, numUnits = 0;   // numSlots: BwBlocked's and these; units: panels or segments
+};
 
 // Device format of bsmr_backward_attach_blocks (csrc/blocked_capi.hpp).  Residue lists: [0] the rows outside panels with
 // blocks (destination = the row of Y), [1] the rows of panels with blocks (destination = their staging row); the chunk
@@ -32,6 +42,11 @@ struct BwBlocked {
     uint32_t numPanels = 0, numItems[2] = {0, 0}, numSplits[2] = {0, 0}, numSlots = 0;
     uint32_t segmentBlocks = 0, numSegs = 0, numSplitPanels = 0, numPartials = 0;   // numPartials: segments of split panels
     bsmr_blocked_stats stats{};
+    // host copies of items[1], panelRows and segs, and what is built from them on demand (not part of the statistics)
+    std::vector<bsmr::BwItem> hostItems1;
+    std::vector<uint32_t> hostPanelRows;
+    std::vector<bsmr::BlkSegment> hostSegs;
+    std::unique_ptr<BwAttnBlk> attn;
 };
 
 struct bsmr_backward {

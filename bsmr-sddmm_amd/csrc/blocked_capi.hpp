@@ -304,6 +304,9 @@ int bsmr_backward_attach_blocks_split(bsmr_backward* bw, const bsmr_rphm_desc* d
             f->numItems[l] = (uint32_t)items[l].size();
             f->numSplits[l] = (uint32_t)splits[l].size();
         }
+        f->hostItems1 = std::move(items[1]);   // for bsmr_sparse_attention_qkv_blocked_16's lists, built on its first call
+        f->hostPanelRows = std::move(panelRows);
+        f->hostSegs = std::move(segs);
     } catch (const std::bad_alloc&) {
         return BSMR_ERR_OOM;
     }

@@ -257,6 +257,9 @@ HIP_SYMBOLS = {
     "bsmr_sparse_attention_qkv_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bsmr_sparse_attention_qkv_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
                                      [C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_blocked_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bsmr_sparse_attention_qkv_blocked_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
+                                             [C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_qkv_kv8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
                                       [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_qkv_kv8_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
@@ -945,6 +948,21 @@ def sparse_attention_qkv_16(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt_pt
     _check(hip().bsmr_sparse_attention_qkv_16(bw, K, Kv, scale, Q_ptr or None, Kt_ptr or None, V_ptr or None, O_ptr or None,
                                               m_ptr or None, s_ptr or None, num_batches, mode, stream),
            "bsmr_sparse_attention_qkv_16")
+
+
+# --- one-pass sparse attention over the RPHM's dense blocks: both products of the block part on the MFMA ---
+def sparse_attention_qkv_blocked_reserve(bw, K: int, Kv: int, num_batches: int = 1):
+    """workspace of sparse_attention_qkv_blocked_16 with (K, Kv, num_batches), and the lists its first call would build"""
+    _check(hip().bsmr_sparse_attention_qkv_blocked_reserve(bw, K, Kv, num_batches), "bsmr_sparse_attention_qkv_blocked_reserve")
+
+
+def sparse_attention_qkv_blocked_16(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt_ptr: int, V_ptr: int, O_ptr: int,
+                                    m_ptr: int, s_ptr: int, num_batches: int = 1, stream: int = 0, mode=COMPUTE_F16):
+    """sparse_attention_qkv_16 on a handle with attached blocks: the entries in the RPHM's 16 x 16 blocks on the MFMA, the
+    residue through the one-pass gather, merged row by row"""
+    _check(hip().bsmr_sparse_attention_qkv_blocked_16(bw, K, Kv, scale, Q_ptr or None, Kt_ptr or None, V_ptr or None,
+                                                      O_ptr or None, m_ptr or None, s_ptr or None, num_batches, mode, stream),
+           "bsmr_sparse_attention_qkv_blocked_16")
 
 
 # --- one-pass sparse attention on a quantised KV cache: Kt and V as fp8 bytes or e2m1 nibbles, with or without MX block

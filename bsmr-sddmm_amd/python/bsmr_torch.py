@@ -306,7 +306,7 @@ class SparseOperator:
         return _SoftmaxSpMM.apply(self, values, X, scale)
 
     def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None, fused: bool = False,
-                  out_dtype=None, Kt_scale=None, V_scale=None, one_pass: bool = False) -> torch.Tensor:
+                  out_dtype=None, Kt_scale=None, V_scale=None, one_pass: bool = False, blocks: bool = False) -> torch.Tensor:
         """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
         positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row.
         fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order.
@@ -316,7 +316,13 @@ class SparseOperator:
         are never stored in the forward; Q fp16 or bf16, K and Kv at most 512, no out_dtype (O has Q's dtype).  Kt and V are
         both of Q's dtype (no scales), or both one fp8 dtype (Kt_scale and V_scale both given or both None), or both fp4
         (both scales): the quantised forms read the cache bytes in place (bsmr_sparse_attention_qkv_kv8 / _kv8_mx /
-        _kv4_mx) and give a gradient to Q alone."""
+        _kv4_mx) and give a gradient to Q alone.
+        blocks=True (with one_pass=True on a blocked=True operator, 16-bit Kt and V only): the entries in the RPHM's dense
+        16 x 16 blocks run both products on the MFMA (bsmr_sparse_attention_qkv_blocked_16), the residue takes the
+        one-pass gather; segment_blocks is honoured.  The same function in another summation order; the backward is
+        one_pass=True's.  The default False keeps every path and bit."""
+        if blocks:
+            self._check_blocks(Kt, V, fused, one_pass, Kt_scale, V_scale)
         if one_pass:
             if fused:
                 raise ValueError("fused=True with one_pass=True: they are two different paths, choose one")
@@ -324,6 +330,8 @@ class SparseOperator:
             scale = Q.shape[-1] ** -0.5 if scale is None else scale
             if quantised:
                 return _AttentionOnePassKv.apply(self, Q, Kt, V, scale, Kts, Vs)
+            if blocks:
+                return _AttentionOnePassBlocks.apply(self, Q, Kt, V, scale)
             return _AttentionOnePass.apply(self, Q, Kt, V, scale)
         self._no_scale(None if _is8(Kt) or _is4(Kt) else Kt_scale, "Kt_scale", "Kt")   # both refused before any device work
         self._no_scale(None if _is8(V) or _is4(V) else V_scale, "V_scale", "V")
@@ -652,8 +660,24 @@ class SparseOperator:
                              "without; one scaled operand beside an unscaled one goes through one_pass=False")
         return True, self._check_scale(Kt_scale, "Kt_scale", Kt), self._check_scale(V_scale, "V_scale", V)
 
-    def _attention_qkv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale):
-        """(O, m, s) of the one-pass forward; O (M, Kv) or (b, M, Kv) in Q's dtype, m and s (M,) or (b, M) fp32"""
+    def _check_blocks(self, Kt, V, fused, one_pass, Kt_scale, V_scale):
+        """the limits attention(blocks=True) adds to one_pass=True's, named before any device work"""
+        if fused:
+            raise ValueError("fused=True with blocks=True: blocks=True is a form of one_pass=True")
+        if not one_pass:
+            raise ValueError("blocks=True needs one_pass=True: the composed path puts its last step on the blocks by itself")
+        if not self.blocked:
+            raise ValueError("blocks=True needs an operator built with blocked=True: the handle has no attached blocks")
+        for t, name in ((Kt, "Kt"), (V, "V")):
+            if isinstance(t, torch.Tensor) and (_is8(t) or _is4(t)):
+                raise ValueError(f"{name}: dtype {t.dtype} - blocks=True takes torch.float16 or torch.bfloat16 keys and "
+                                 "values; a quantised cache goes through blocks=False")
+        if Kt_scale is not None or V_scale is not None:
+            raise ValueError("Kt_scale / V_scale: blocks=True takes 16-bit keys and values, which have no MX block scales")
+
+    def _attention_qkv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, blocks: bool = False):
+        """(O, m, s) of the one-pass forward; O (M, Kv) or (b, M, Kv) in Q's dtype, m and s (M,) or (b, M) fp32.
+        blocks: through bsmr_sparse_attention_qkv_blocked_16"""
         b, K = self._check(Q, "Q", self.M, None)
         _, K2 = self._check(Kt, "Kt", self.N, (b,))
         _, Kv = self._check(V, "V", self.N, (b,))
@@ -668,8 +692,9 @@ class SparseOperator:
         O = torch.empty((self.M, Kv) if b is None else (b, self.M, Kv), dtype=Q.dtype, device=self.device)
         m = torch.empty((self.M,) if b is None else (b, self.M), dtype=torch.float32, device=self.device)
         s = torch.empty_like(m)
-        eng.sparse_attention_qkv_16(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(),
-                                    m.data_ptr(), s.data_ptr(), b or 1, self._stream(), mode=_MODE16[Q.dtype])
+        call = eng.sparse_attention_qkv_blocked_16 if blocks else eng.sparse_attention_qkv_16
+        call(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(), m.data_ptr(), s.data_ptr(), b or 1,
+             self._stream(), mode=_MODE16[Q.dtype])
         return O, m, s
 
     def _attention_qkv_kv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, Kts=None, Vs=None):
@@ -942,6 +967,17 @@ class _AttentionOnePass(torch.autograd.Function):
         if need_q or need_k:
             dQ, dKt = op._sddmm_backward(dP, Q, Kt, need_q, need_k)
         return None, dQ, dKt, dV, None
+
+
+class _AttentionOnePassBlocks(_AttentionOnePass):
+    """attention(one_pass=True, blocks=True): the forward over the RPHM's blocks; _AttentionOnePass's backward on the
+    saved O, m, s"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, Q, Kt, V, scale):
+        O, m, s = op._attention_qkv(Q, Kt, V, scale, blocks=True)
+        ctx.op, ctx.scale = op, float(scale)
+        ctx.save_for_backward(Q, Kt, V, O, m, s)
+        return O
 
 
 class _AttentionOnePassKv(torch.autograd.Function):

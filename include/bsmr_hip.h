@@ -790,6 +790,60 @@ int bsmr_sparse_attention_qkv_16(bsmr_backward *bw, uint32_t K, uint32_t Kv, flo
                                  const void *Kt16_dev, const void *V16_dev, void *O16_dev, float *m_dev, float *s_dev,
                                  uint32_t num_batches, int compute_mode, void *stream);
 
+/* ---- One-pass sparse attention over blocks: both products of the RPHM's dense blocks on the MFMA (revision 5, added
+ *      without any layout change) ----
+ * bsmr_sparse_attention_qkv_16 on a handle with attached blocks (bsmr_backward_attach_blocks[_split]): the same function,
+ * arguments, formats and limits (K, Kv multiples of 32 in 32 ... 512), another summation order.  The entries of a row that
+ * lie in its panel's 16 x 16 blocks are served block by block - a row of Kt and a row of V are read once per block and
+ * shared by the panel's 16 rows - and its residue entries by the kernel of bsmr_sparse_attention_qkv_16 over the residue
+ * lists of "Blocked SpMM".  No score is stored; nothing of size nnz is written, read or allocated.
+ * Per row r (u = 2^-24, every step one IEEE fp32 operation unless said otherwise, the accurate expf):
+ *   A row in no panel with blocks: bsmr_sparse_attention_qkv_16's contract over its residue list (= its CSR entries when
+ *   its panel has no block), bit for bit.  On a handle whose RPHM has no block at all the two calls agree bit for bit.
+ *   A row of a panel with blocks gives one partial (m_c, s_c, acc_c) per residue chunk (that contract; a row without
+ *   residue gives none) and one per unit: the whole panel, or with segment_blocks = S >= 1 each of its segments.
+ *   A unit takes its blocks in order with a running (m, s, acc) from (-inf, 0, +0).  Per block, for the row's 16 cells j:
+ *     p_j = sum_k Kt[c_j,k] Q[r,k] on v_mfma_f32_16x16x32_f16 / _bf16, K/32 steps of 32 elements in ascending k into one
+ *           fp32 accumulator from +0.  The order inside a step is the instruction's and is not pinned: the contract for
+ *           p_j is the bound below.  z_j = fl(scale p_j) for a stored cell; an empty cell or a padding column is -inf BY
+ *           SELECT, so a NaN in Kt[c] reaches exactly the rows that store column c.
+ *     m' = max(m, max_j z_j), NaN once any z of the row was NaN (the flag rule of "Sparse row softmax"); alpha =
+ *           expf(fl(m - m')) (1 while m = -inf); s = fl(s alpha), acc = fl(acc alpha) (skipped when m' = m);
+ *           e_j = expf(fl(z_j - m')) (0 while m' = -inf).
+ *     s = s + t, t = (x_0 + x_1) + (x_2 + x_3), x_q = ((e_q + e_4+q) + e_8+q) + e_12+q (+ commutes: lane order is free).
+ *     acc_k = fmaf(e_j, V[c_j,k], acc_k) for j = 0 ... 15 in order (v_mfma_f32_16x16x4_f32: V widened exactly, one rounding
+ *           per step), EMPTY CELLS INCLUDED with e_j = 0 (a padding column enters as 0 * 0).
+ *   Empty-cell rule, as in "Blocked SpMM": a non-finite V[c,k] makes acc_k NaN in every row of a unit that holds c as a
+ *   block column, whether the row stores it or not - unless the row stores no cell of that unit at all: its partial has
+ *   m_c = -inf and is skipped.  The skip of tiles met while m = -inf that bsmr_sparse_attention_qkv_16 has does not exist
+ *   for blocks.
+ *   Merge, in the order residue chunks (chunk order) then units (segment order), the statements of
+ *   bsmr_sparse_attention_qkv_16: m = max_c m_c (NaN if any is), beta_c = expf(fl(m_c - m)), a partial with m_c = -inf is
+ *   skipped, s = sum_c fl(s_c beta_c), acc = sum_c fl(acc_c beta_c) from +0, O_k = round16(acc_k / s).
+ * Exact cases: equal scores give s = n and round16(fl(sum of the row's V rows) / n) when that sum is exact in fp32; an
+ * empty or all -inf row gives O = +0, m = -inf, s = 0.  One writer per element, no atomics: bitwise reproducible call to
+ * call, stream to stream and batch to batch.
+ * Forward bound against fp64 on the same 16-bit inputs, with A_t, d, Z_r, w64, u16 of "One-pass sparse
+ * attention" and, for the row: n = 16 (blocks of its panel) + its residue entries, T = (blocks of its panel) + ceil(residue
+ * entries / 16), P = its partials (residue chunks + units):
+ *   |m - m64| <= d = |scale| (K + 1) u max_t A_t.  For block cells this rests on a supposition: one 16x16x32 step errs by
+ *   no more than 32 sequential fp32 roundings of its exact products.
+ *   |O_k - O64_k| <= [(exp(2 d) - 1) + exp(2 d) (2 n + 2 P + 6 T + 2 Z_r + 13) u] sum_t w64_t |V[c_t,k]|
+ *                    + (n + P + 2 T + 2) 2^-126 max_t |V[c_t,k]|, then + u16 |O_k| (+ 2^-25 in fp16);
+ *   |s - s64| <= [(exp(2 d) - 1) + exp(2 d) (n + P + 3 T + Z_r + 7) u] s64.
+ * Workspace: the partial area of bsmr_sparse_attention_qkv_16's kernel for the residue chunks, then the unit partials
+ * [b][16 units][Kv], their s and m [b][16 units]; bsmr_sparse_attention_qkv_blocked_reserve(K, Kv, num_batches) sizes it and
+ * builds the call's lists (done by the first call otherwise); afterwards covered calls allocate nothing.  The layouts,
+ * reserves and statistics of every other call are unchanged.
+ * Checked before any device call, in this order: a NULL handle or a non-finite scale (BSMR_ERR_INVALID_ARG), K or Kv
+ * (BSMR_ERR_UNSUPPORTED_K), compute_mode, more than 65535 batches, a handle without attached blocks (BSMR_ERR_BAD_PLAN),
+ * then the pointers as bsmr_sparse_attention_qkv_16.  num_batches = 0 is a no-op.  With nnz = 0 the inputs may be NULL and
+ * the call writes O = +0, m = -inf, s = 0. */
+int bsmr_sparse_attention_qkv_blocked_reserve(bsmr_backward *bw, uint32_t K, uint32_t Kv, uint32_t num_batches);
+int bsmr_sparse_attention_qkv_blocked_16(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                         const void *Kt16_dev, const void *V16_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                         uint32_t num_batches, int compute_mode, void *stream);
+
 /* ---- One-pass sparse attention on fp8, MXFP8 and MXFP4 keys and values (revision 5, added without any layout change) ----
  * bsmr_sparse_attention_qkv_16 with Kt and V as a quantised KV cache holds them, in the formats of "fp8 keys and values",
  * "MX block scales" and "MXFP4 keys and values" below: the kernel reads the cache bytes and widens in registers.  No 16-bit

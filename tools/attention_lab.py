@@ -14,7 +14,11 @@ the same process.  `agree` is max |O_fused - O_composed| / max |O|.
 fused path (quantised sddmm, which first writes a 16-bit copy of Kt and then P, + the quantised fused call) against the
 one-pass call on the same codes (bsmr_sparse_attention_qkv_kv8 / _kv8_mx / _kv4_mx), the fused path first.  kt16_bytes and
 p_bytes are what the one-pass forward neither allocates nor moves, per batch: the 16-bit copy of Kt and the scores.
-Usage: python tools/attention_lab.py [--kv FORMAT] [--out FILE] [shape ...]   (one JSON line per shape)"""
+--blocks S: instead of the above, the 16-bit forward from Q, Kt, V on blocked=True operators built from the pipeline's RPHM,
+attached whole (segment_blocks 0) and in segments of S blocks: the fused path, the one-pass call and the blocked one-pass
+call (bsmr_sparse_attention_qkv_blocked_16) side by side in one job, K = Kv = 128, b = 1 and 8, fp16 and bf16.  coverage
+is the blocks' entries / nnz: what the blocked kernel serves; the rest is the residue on the one-pass gather.
+Usage: python tools/attention_lab.py [--kv FORMAT | --blocks S] [--out FILE] [shape ...]   (one JSON line per shape)"""
 import argparse
 import json
 import sys
@@ -148,17 +152,65 @@ def main_kv(names, out, kv):
         torch.cuda.empty_cache()
 
 
+def main_blocks(names, out, S):
+    for name in names:
+        gen, kwargs, _ = SHAPES[name]
+        rows, cols, ro, ci = getattr(synth, gen)(**kwargs)
+        ro = np.ascontiguousarray(ro, dtype=np.uint32)
+        ci = np.ascontiguousarray(ci, dtype=np.uint32)
+        Kw = 128
+        scale = Kw ** -0.5
+        csr = eng.CSR.from_arrays(rows, cols, ro, ci)
+        ops = {seg: bsmr_torch.SparseOperator(csr, device=0, blocked=True, segment_blocks=seg) for seg in (0, S)}
+        st = eng.backward_blocked_stats(ops[S]._bw)
+        line = {"shape": name, "M": rows, "N": cols, "nnz": int(ci.size), "K": Kw, "blocks": st["blocks"],
+                "coverage": round(st["block_entries"] / max(int(ci.size), 1), 4), "panels_with_blocks": st["panels_with_blocks"],
+                "max_blocks_per_panel": st["max_blocks_per_panel"], "segments": st["segments"]}
+        us = {}
+        for b in (1, 8):
+            for seg, op in ops.items():
+                eng.sparse_attention_reserve(op._bw, Kw, b)
+                eng.sparse_attention_qkv_blocked_reserve(op._bw, Kw, Kw, b)
+            for dtype, tag in ((torch.float16, "f16"), (torch.bfloat16, "bf16")):
+                g = torch.Generator(device=dev).manual_seed(7)
+                Q, Kt, V = (torch.randn(b, n, Kw, device=dev, generator=g).to(dtype) for n in (rows, cols, cols))
+                key = f"b{b}_{tag}"
+                op = ops[0]
+                us[f"fwd_fused_{key}"] = windows(lambda: op._attention(op._sddmm(Q, Kt), V, scale))
+                us[f"fwd_one_pass_{key}"] = windows(lambda: op._attention_qkv(Q, Kt, V, scale))
+                Of = op._attention(op._sddmm(Q, Kt), V, scale)[0].float()
+                for seg, o in ops.items():
+                    us[f"fwd_blocks_S{seg}_{key}"] = windows(lambda: o._attention_qkv(Q, Kt, V, scale, blocks=True))
+                    Ob = o._attention_qkv(Q, Kt, V, scale, blocks=True)[0].float()
+                    line[f"agree_blocks_S{seg}_{key}"] = float((Ob - Of).abs().max() / Of.abs().max())
+                del Q, Kt, V, Of, Ob
+        line["us"] = us
+        text = json.dumps(line)
+        print(text, flush=True)
+        if out:
+            with open(out, "a") as f:
+                f.write(text + "\n")
+        del ops, op, o
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--kv", choices=("fp8", "mxfp8", "mxfp4"), default=None,
                     help="time the forward on a quantised KV cache: fused path against one-pass")
+    ap.add_argument("--blocks", type=int, default=None, metavar="S",
+                    help="time the 16-bit forward over the RPHM's blocks (segment_blocks 0 and S) beside fused and one-pass")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("shapes", nargs="*", help=f"any of {', '.join(SHAPES)} (default: all)")
     args = ap.parse_args()
     unknown = [n for n in args.shapes if n not in SHAPES]
     if unknown:
         ap.error(f"unknown shape(s) {unknown}")
-    if args.kv:
+    if args.blocks is not None:
+        if args.kv or args.blocks < 1:
+            ap.error("--blocks takes S >= 1 and excludes --kv")
+        main_blocks(args.shapes or list(SHAPES), args.out, args.blocks)
+    elif args.kv:
         main_kv(args.shapes or list(SHAPES), args.out, args.kv)
     else:
         main(args.shapes or list(SHAPES), args.out)
