@@ -11,6 +11,24 @@ hipError_t bsmrLaunchAttnQkv(const void* items, uint32_t numItems, const void* s
                              float* s, float* partial, float* sPart, float* mPart, uint32_t K, uint32_t Kv, uint32_t M,
                              uint32_t N, uint32_t numSlots, uint32_t numBatches, bool bf16, hipStream_t stream);
 
+// The one entry of csrc/attention_qkv_bwd.hip: attnQkvBwdQ over the row direction's lists when dQ is asked for, attnQkvBwdKV
+// over the column direction's when dKt or dV is, each followed by attnQkvBwdReduce for its split destinations
+// (csrc/attention_qkv_bwd_kernels.hpp).  A gradient that is NULL is not computed.  D [b][M]: dO_r . O_r, already written on
+// the stream; rowPart [b][rows.numSlots][K] and colPart [b][cols.numSlots][K + Kv]: the chunk partials, written here.
+struct BsmrAttnBwdLists {   // one direction of the handle, on the device
+    const void* items;      // BwItem[numItems]
+    uint32_t numItems;
+    const void* splits;     // BwSplit[numSplits]
+    uint32_t numSplits;
+    const uint32_t* src;    // colIndices (rows) or cscRows (columns)
+    uint32_t numSlots;
+};
+hipError_t bsmrLaunchAttnQkvBwd(const BsmrAttnBwdLists& rows, const BsmrAttnBwdLists& cols, float scale, const uint16_t* Q,
+                                const uint16_t* Kt, const uint16_t* V, const uint16_t* dO, const float* m, const float* s,
+                                const float* D, uint16_t* dQ, uint16_t* dKt, uint16_t* dV, float* rowPart, float* colPart,
+                                uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numBatches, bool bf16,
+                                hipStream_t stream);
+
 // A row of a panel with blocks, as attnQkvBlkMerge (csrc/attention_qkv_blocked_kernels.hpp) merges it: its residue chunks
 // on the slots resFirst ... of attnQkv's partial area, then its block units on the rows blkFirst, blkFirst + 16, ... of
 // the block partial area (a unit owns 16 consecutive rows, one per row of its panel).

@@ -266,7 +266,10 @@ HIP_SYMBOLS = {
                                          [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_qkv_kv4_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
                                          [C.c_uint32, C.c_int, C.c_void_p]),
-    "bsmr_widen_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_backward_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "bsmr_sparse_attention_qkv_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 10 +
+                                              [C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_widen_fp8": (C.c_int,[C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
     "bsmr_sddmm_b8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
                                 C.c_void_p]),
     "bsmr_spmm_x8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
@@ -991,6 +994,24 @@ def sparse_attention_qkv_kv4_mx(bw, K: int, Kv: int, scale: float, Q_ptr: int, K
     _check(hip().bsmr_sparse_attention_qkv_kv4_mx(bw, K, Kv, scale, Q_ptr or None, Kt4_ptr or None, Kts_ptr or None,
                                                   V4_ptr or None, Vs_ptr or None, O_ptr or None, m_ptr or None, s_ptr or None,
                                                   num_batches, mode, stream), "bsmr_sparse_attention_qkv_kv4_mx")
+
+
+# --- one-pass backward of sparse attention: dQ, dKt, dV with scores and weights in registers only ---
+def sparse_attention_qkv_backward_reserve(bw, K: int, Kv: int, num_batches: int = 1):
+    """workspace of sparse_attention_qkv_backward_16 with (K, Kv, num_batches): the chunk partials of both directions and D"""
+    _check(hip().bsmr_sparse_attention_qkv_backward_reserve(bw, K, Kv, num_batches),
+           "bsmr_sparse_attention_qkv_backward_reserve")
+
+
+def sparse_attention_qkv_backward_16(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt_ptr: int, V_ptr: int, O_ptr: int,
+                                     dO_ptr: int, m_ptr: int, s_ptr: int, dQ_ptr: int, dKt_ptr: int, dV_ptr: int,
+                                     num_batches: int = 1, stream: int = 0, mode=COMPUTE_F16):
+    """dQ, dKt, dV from fp16 / bf16 Q, Kt, V, O, dO and the forward's (m, s); a gradient pointer of 0 is not computed;
+    K, Kv multiples of 32 up to 256"""
+    _check(hip().bsmr_sparse_attention_qkv_backward_16(bw, K, Kv, scale, Q_ptr or None, Kt_ptr or None, V_ptr or None,
+                                                       O_ptr or None, dO_ptr or None, m_ptr or None, s_ptr or None,
+                                                       dQ_ptr or None, dKt_ptr or None, dV_ptr or None, num_batches, mode,
+                                                       stream), "bsmr_sparse_attention_qkv_backward_16")
 
 
 # --- fp8 keys and values: the column-side operand as OCP fp8 bytes (fmt FP8_E4M3 / FP8_E5M2), widened exactly to the

@@ -124,6 +124,7 @@ _EMAX8 = {torch.float8_e4m3fn: 8, torch.float8_e5m2: 15}   # exponent of the lar
 _SCALE_DTYPES = (torch.uint8,) + ((torch.float8_e8m0fnu,) if hasattr(torch, "float8_e8m0fnu") else ())
 MX_BLOCK = 32
 ONE_PASS_MAX_K = 512   # attention(one_pass=True): one wave holds a whole row of Q (K) and of the accumulators (Kv)
+ONE_PASS_BACKWARD_MAX_K = 256   # ... with one_pass_backward=True: a lane of the column side holds (K + Kv) / 4 accumulators
 _FP4 = getattr(torch, "float4_e2m1fn_x2", None)   # two e2m1 codes per byte, element 2i in the low nibble
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # the magnitude of code 0 .. 7; bit 3 is the sign
 _E2M1_TIES = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)   # the midpoint between codes i and i + 1
@@ -306,7 +307,8 @@ class SparseOperator:
         return _SoftmaxSpMM.apply(self, values, X, scale)
 
     def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None, fused: bool = False,
-                  out_dtype=None, Kt_scale=None, V_scale=None, one_pass: bool = False, blocks: bool = False) -> torch.Tensor:
+                  out_dtype=None, Kt_scale=None, V_scale=None, one_pass: bool = False, blocks: bool = False,
+                  one_pass_backward: bool = False) -> torch.Tensor:
         """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
         positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row.
         fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order.
@@ -320,7 +322,13 @@ class SparseOperator:
         blocks=True (with one_pass=True on a blocked=True operator, 16-bit Kt and V only): the entries in the RPHM's dense
         16 x 16 blocks run both products on the MFMA (bsmr_sparse_attention_qkv_blocked_16), the residue takes the
         one-pass gather; segment_blocks is honoured.  The same function in another summation order; the backward is
-        one_pass=True's.  The default False keeps every path and bit."""
+        one_pass=True's.  The default False keeps every path and bit.
+        one_pass_backward=True (with one_pass=True, 16-bit Kt and V, blocks=False, K and Kv at most 256): the backward is one
+        call as well (bsmr_sparse_attention_qkv_backward_16) - dQ, dKt and dV from Q, Kt, V, O, dO and the saved (m, s) with
+        scores and weights in registers only, nothing of size nnz in the whole step.  The same gradients in another
+        summation order.  The default False keeps every path and bit."""
+        if one_pass_backward:
+            self._check_one_pass_backward(Q, Kt, V, one_pass, blocks)
         if blocks:
             self._check_blocks(Kt, V, fused, one_pass, Kt_scale, V_scale)
         if one_pass:
@@ -332,6 +340,8 @@ class SparseOperator:
                 return _AttentionOnePassKv.apply(self, Q, Kt, V, scale, Kts, Vs)
             if blocks:
                 return _AttentionOnePassBlocks.apply(self, Q, Kt, V, scale)
+            if one_pass_backward:
+                return _AttentionOnePassBwd.apply(self, Q, Kt, V, scale)
             return _AttentionOnePass.apply(self, Q, Kt, V, scale)
         self._no_scale(None if _is8(Kt) or _is4(Kt) else Kt_scale, "Kt_scale", "Kt")   # both refused before any device work
         self._no_scale(None if _is8(V) or _is4(V) else V_scale, "V_scale", "V")
@@ -660,6 +670,22 @@ class SparseOperator:
                              "without; one scaled operand beside an unscaled one goes through one_pass=False")
         return True, self._check_scale(Kt_scale, "Kt_scale", Kt), self._check_scale(V_scale, "V_scale", V)
 
+    def _check_one_pass_backward(self, Q, Kt, V, one_pass, blocks):
+        """the limits attention(one_pass_backward=True) adds to one_pass=True's, named before any device work"""
+        if not one_pass:
+            raise ValueError("one_pass_backward=True needs one_pass=True: it is the backward of the one-pass forward")
+        if blocks:
+            raise ValueError("one_pass_backward=True with blocks=True: the one-pass backward has no form over the RPHM's "
+                             "blocks, blocks=True keeps one_pass=True's default backward")
+        for t, name in ((Kt, "Kt"), (V, "V")):
+            if isinstance(t, torch.Tensor) and (_is8(t) or _is4(t)):
+                raise ValueError(f"{name}: dtype {t.dtype} - one_pass_backward=True takes torch.float16 or torch.bfloat16 "
+                                 "keys and values; a quantised cache keeps one_pass=True's default backward")
+        for t, name in ((Q, "Q"), (Kt, "Kt"), (V, "V")):
+            if isinstance(t, torch.Tensor) and t.dim() in (2, 3) and t.shape[-1] > ONE_PASS_BACKWARD_MAX_K:
+                raise ValueError(f"{name}: {t.shape[-1]} features - one_pass_backward=True takes K and Kv in "
+                                 f"32 ... {ONE_PASS_BACKWARD_MAX_K}")
+
     def _check_blocks(self, Kt, V, fused, one_pass, Kt_scale, V_scale):
         """the limits attention(blocks=True) adds to one_pass=True's, named before any device work"""
         if fused:
@@ -725,6 +751,25 @@ class SparseOperator:
             eng.sparse_attention_qkv_kv8(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), *out,
                                          mode=_MODE16[Q.dtype], fmt=_MODE8[Kt.dtype])
         return O, m, s
+
+    def _attention_qkv_backward(self, Q, Kt, V, O, dO, m, s, scale, need_q=True, need_k=True, need_v=True):
+        """(dQ, dKt, dV) of the one-pass backward in Q's dtype, None where not needed; Q, Kt, V, O, m, s as the one-pass
+        forward took and gave them, dO contiguous in O's dtype"""
+        b, K = self._check(Q, "Q", self.M, None)
+        self._check(Kt, "Kt", self.N, (b,))
+        _, Kv = self._check(V, "V", self.N, (b,))
+        self._check(O, "O", self.M, (b,))
+        self._check(dO, "dO", self.M, (b,))
+        if dO.shape != O.shape or dO.dtype != O.dtype:
+            raise ValueError(f"dO: {dO.dtype} {tuple(dO.shape)}, expected O's {O.dtype} {tuple(O.shape)}")
+        dQ = torch.empty_like(Q) if need_q else None
+        dKt = torch.empty_like(Kt) if need_k else None
+        dV = torch.empty_like(V) if need_v else None
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        eng.sparse_attention_qkv_backward_16(self._bw, K, Kv, float(scale), Q.data_ptr(), Kt.data_ptr(), V.data_ptr(),
+                                             O.data_ptr(), dO.data_ptr(), m.data_ptr(), s.data_ptr(), ptr(dQ), ptr(dKt),
+                                             ptr(dV), b or 1, self._stream(), mode=_MODE16[Q.dtype])
+        return dQ, dKt, dV
 
     def _attention_backward(self, v, m, s, dW, O, dO, scale):
         """(dP, W) of the fused backward; dP is written over dW (the same tensor is returned)"""
@@ -966,6 +1011,20 @@ class _AttentionOnePass(torch.autograd.Function):
         dQ = dKt = None
         if need_q or need_k:
             dQ, dKt = op._sddmm_backward(dP, Q, Kt, need_q, need_k)
+        return None, dQ, dKt, dV, None
+
+
+class _AttentionOnePassBwd(_AttentionOnePass):
+    """attention(one_pass=True, one_pass_backward=True): _AttentionOnePass's forward and saved tensors; the backward is one
+    call that stores no score either"""
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        need_q, need_k, need_v = ctx.needs_input_grad[1:4]
+        if not (need_q or need_k or need_v):
+            return None, None, None, None, None
+        Q, Kt, V, O, m, s = ctx.saved_tensors
+        dQ, dKt, dV = ctx.op._attention_qkv_backward(Q, Kt, V, O, _grad(dO, O.dtype), m, s, ctx.scale, need_q, need_k, need_v)
         return None, dQ, dKt, dV, None
 
 

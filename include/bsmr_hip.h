@@ -891,6 +891,44 @@ int bsmr_sparse_attention_qkv_kv4_mx(bsmr_backward *bw, uint32_t K, uint32_t Kv,
                                      const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev,
                                      uint32_t num_batches, int compute_mode, void *stream);
 
+/* ---- One-pass backward of sparse attention (revision 5, added without any layout change) ----
+ * dQ, dKt and dV of O = softmax_rows(scale Q Kt^T at S's stored positions) V from Q, Kt, V, the forward's O, m and s
+ * (bsmr_sparse_attention_qkv_16 or its blocked form) and dO, with scores and weights in registers only: nothing of size
+ * nnz is allocated, written or read, and there are no atomics.  Same handle: its row lists serve dQ, its column lists
+ * (csc_rows alone - no value array is read) dKt and dV.  Q, O's cotangent dO and every gradient are fp16 or bf16, all of
+ * compute_mode's format; Q, dQ [b][M][K], Kt, dKt [b][N][K], V, dV [b][N][Kv], O, dO [b][M][Kv]; m, s [b][M] fp32.
+ * K and Kv are multiples of 32 in 32 ... 256, anything else is BSMR_ERR_UNSUPPORTED_K: the limit is this call's (a lane of
+ * the column side holds (K + Kv) / 4 fp32 accumulators), the forward's 512 is unchanged.
+ * Per entry t = (r, c), every step one IEEE fp32 operation, the accurate expf:
+ *   p_t  = the p_t of "One-pass sparse attention", bit for bit (the same operands in the same order), z_t = fl(scale p_t);
+ *   e_t  = expf(fl(z_t - m_r));  w_t = fl(e_t / s_r), and 0 when m_r = -inf;
+ *   dW_t = sum_k dO[r,k] V[c,k] in p_t's order over Kv;  D_r = sum_k dO[r,k] O[r,k] in the order of
+ *          bsmr_sparse_attention_backward_16 ("Fused sparse attention"), on O as it was stored;
+ *   dz_t = fl(fl(w_t fl(dW_t - D_r)) scale);
+ *   dQ[r] = sum_t dz_t Kt[c_t],  dKt[c] = sum_t dz_t Q[r_t],  dV[c] = sum_t w_t dO[r_t]: each term one fmaf, each sum
+ *          rounded once to 16 bits.  Summation order of a list (a row's entries in CSR order, a column's in ascending
+ *          row): sixteen chains from +0, chain j over the entries j, j + 16, j + 32, ... of the list (of each chunk of a
+ *          list longer than BSMR_BACKWARD_CHUNK), added as a butterfly over the chain offsets 1, 2, 4, 8; chunk sums are
+ *          added in chunk order.  This is not bsmr_spmm's sequential chain.
+ * The row side and the column side see the same bits of w_t and dz_t.  An entry whose w_t is exactly 0 (a dead row, a -inf
+ * score, an underflown weight) is left out of every sum by a select, not multiplied by 0.  A NaN in row r of Q or dO
+ * reaches dQ[r] and the dKt / dV rows of the columns row r stores, and no other row.  A row or column without entries gets
+ * +0.  One writer per element: bitwise reproducible call to call, stream to stream and batch to batch.
+ * Any of dQ16_dev, dKt16_dev, dV16_dev may be NULL: that gradient is not computed (the row kernel runs for dQ alone, the
+ * column kernel for dKt or dV); all three NULL is a no-op.
+ * Workspace, in floats: the row partials [b][row chunk slots][K], the column partials [b][column chunk slots][K + Kv], then
+ * D [b][M]; bsmr_sparse_attention_qkv_backward_reserve(K, Kv, num_batches) sizes it, afterwards covered calls allocate
+ * nothing.  The layouts and reserves of every other call are unchanged.
+ * Checked before any device call, in this order: a NULL handle or a non-finite scale (BSMR_ERR_INVALID_ARG), K or Kv
+ * (BSMR_ERR_UNSUPPORTED_K), compute_mode, more than 65535 batches, then the pointers: 16 bytes for every 16-bit array, 4 for
+ * m and s; the inputs may be NULL only with nnz = 0.  num_batches = 0 is a no-op. */
+int bsmr_sparse_attention_qkv_backward_reserve(bsmr_backward *bw, uint32_t K, uint32_t Kv, uint32_t num_batches);
+int bsmr_sparse_attention_qkv_backward_16(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                          const void *Kt16_dev, const void *V16_dev, const void *O16_dev,
+                                          const void *dO16_dev, const float *m_dev, const float *s_dev, void *dQ16_dev,
+                                          void *dKt16_dev, void *dV16_dev, uint32_t num_batches, int compute_mode,
+                                          void *stream);
+
 /* ---- fp8 keys and values (revision 5, added without any layout change; no reference counterpart) ----
  * The column-side operand - B / Kt of the SDDMM, X / V of the SpMM and of the fused attention - may be OCP fp8, one byte per
  * element, as an fp8 KV cache holds it: fp8_format BSMR_FP8_E4M3 (e4m3fn: no infinity, two NaN codes) or BSMR_FP8_E5M2 (two

@@ -5,7 +5,9 @@ its fused path (sddmm -> softmax_spmm, bsmr_sparse_attention) and, for 16-bit op
 Per (shape, b, dtype):
   fwd     the part in which composed and fused differ, on given scores P: softmax + spmm (raw calls) against the fused call;
   fwdqkv  (16-bit) the whole forward from Q, Kt, V: sddmm + softmax + spmm, sddmm + fused call, the one-pass call;
-  step    the whole step, forward + backward through autograd: attention(Q, Kt, V, fused= / one_pass=).
+  step    the whole step, forward + backward through autograd: attention(Q, Kt, V, fused= / one_pass=), and for 16-bit
+          operands the one-pass step with one_pass_backward=True (bsmr_sparse_attention_qkv_backward_16) beside them;
+  peak    torch.cuda.max_memory_allocated over one step of each path minus what was allocated before it, in bytes.
 p_bytes is the size of the score array per batch (4 nnz): the one-pass forward neither writes nor reads it.
 Microseconds per call, event timing: 3 windows of 20 calls after 5 warm-up calls; every figure is [best, worst] of its
 three windows, so that a difference can be read against the windows' own spread.  The composed path runs first, both in
@@ -18,7 +20,8 @@ p_bytes are what the one-pass forward neither allocates nor moves, per batch: th
 attached whole (segment_blocks 0) and in segments of S blocks: the fused path, the one-pass call and the blocked one-pass
 call (bsmr_sparse_attention_qkv_blocked_16) side by side in one job, K = Kv = 128, b = 1 and 8, fp16 and bf16.  coverage
 is the blocks' entries / nnz: what the blocked kernel serves; the rest is the residue on the one-pass gather.
-Usage: python tools/attention_lab.py [--kv FORMAT | --blocks S] [--out FILE] [shape ...]   (one JSON line per shape)"""
+--steps: only the 16-bit step and peak columns of the first form (fused, one-pass, one-pass with its own backward).
+Usage: python tools/attention_lab.py [--steps | --kv FORMAT | --blocks S] [--out FILE] [shape ...]   (one JSON line per shape)"""
 import argparse
 import json
 import sys
@@ -58,7 +61,18 @@ def windows(fn, warmup=5, iters=20, count=3):
     return [min(us), max(us)]
 
 
-def main(names, out):
+def peak_bytes(fn):
+    """what one call of fn allocates at its peak, over what is allocated when it starts"""
+    fn()
+    torch.cuda.synchronize(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
+    before = torch.cuda.memory_allocated(dev)
+    fn()
+    torch.cuda.synchronize(dev)
+    return torch.cuda.max_memory_allocated(dev) - before
+
+
+def main(names, out, steps_only=False):
     for name in names:
         gen, kwargs, K = SHAPES[name]
         rows, cols, ro, ci = getattr(synth, gen)(**kwargs)
@@ -74,6 +88,8 @@ def main(names, out):
         for b in (1, 8):
             eng.sparse_attention_reserve(op._bw, Kw, b)
             for dtype, tag in ((torch.float32, "f32"), (torch.float16, "f16"), (torch.bfloat16, "bf16")):
+                if steps_only and dtype == torch.float32:
+                    continue
                 g = torch.Generator(device=dev).manual_seed(7)
                 leaf = lambda n: torch.randn(b, n, Kw, device=dev, generator=g).to(dtype).requires_grad_(True)
                 Q, Kt, V = leaf(rows), leaf(cols), leaf(cols)
@@ -81,15 +97,26 @@ def main(names, out):
                 P = op._sddmm(Q.detach(), Kt.detach())
                 Vd = V.detach()
 
-                def step(fused, one_pass=False):
-                    op.attention(Q, Kt, V, fused=fused, one_pass=one_pass).backward(H)
+                def step(fused, one_pass=False, one_pass_backward=False):
+                    op.attention(Q, Kt, V, fused=fused, one_pass=one_pass, one_pass_backward=one_pass_backward).backward(H)
                     Q.grad = Kt.grad = V.grad = None
 
                 key = f"b{b}_{tag}"
+                if dtype != torch.float32:
+                    eng.sparse_attention_qkv_backward_reserve(op._bw, Kw, Kw, b)
+                    us[f"step_fused_{key}"] = windows(lambda: step(True))
+                    us[f"step_one_pass_{key}"] = windows(lambda: step(False, True))
+                    us[f"step_one_pass_bwd_{key}"] = windows(lambda: step(False, True, True))
+                    for path, args in (("fused", (True,)), ("one_pass", (False, True)), ("one_pass_bwd", (False, True, True))):
+                        line[f"peak_{path}_{key}"] = peak_bytes(lambda: step(*args))
+                if steps_only:
+                    del Q, Kt, V, H, P, Vd
+                    continue
                 us[f"fwd_composed_{key}"] = windows(lambda: op._spmm(op._softmax(P, scale), Vd, False))
                 us[f"fwd_fused_{key}"] = windows(lambda: op._attention(P, Vd, scale))
                 us[f"step_composed_{key}"] = windows(lambda: step(False))
-                us[f"step_fused_{key}"] = windows(lambda: step(True))
+                if dtype == torch.float32:
+                    us[f"step_fused_{key}"] = windows(lambda: step(True))
                 Oc = op._spmm(op._softmax(P, scale), Vd, False).float()
                 Of = op._attention(P, Vd, scale)[0].float()
                 line[f"agree_{key}"] = float((Of - Oc).abs().max() / Oc.abs().max())
@@ -98,7 +125,6 @@ def main(names, out):
                     us[f"fwdqkv_composed_{key}"] = windows(lambda: op._spmm(op._softmax(op._sddmm(Qd, Ktd), scale), Vd, False))
                     us[f"fwdqkv_fused_{key}"] = windows(lambda: op._attention(op._sddmm(Qd, Ktd), Vd, scale))
                     us[f"fwdqkv_one_pass_{key}"] = windows(lambda: op._attention_qkv(Qd, Ktd, Vd, scale))
-                    us[f"step_one_pass_{key}"] = windows(lambda: step(False, True))
                     O1 = op._attention_qkv(Qd, Ktd, Vd, scale)[0].float()
                     line[f"agree_one_pass_{key}"] = float((O1 - Oc).abs().max() / Oc.abs().max())
                     del Qd, Ktd, O1
@@ -200,6 +226,7 @@ if __name__ == "__main__":
                     help="time the forward on a quantised KV cache: fused path against one-pass")
     ap.add_argument("--blocks", type=int, default=None, metavar="S",
                     help="time the 16-bit forward over the RPHM's blocks (segment_blocks 0 and S) beside fused and one-pass")
+    ap.add_argument("--steps", action="store_true", help="only the 16-bit step and peak columns of the default form")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("shapes", nargs="*", help=f"any of {', '.join(SHAPES)} (default: all)")
     args = ap.parse_args()
@@ -213,4 +240,4 @@ if __name__ == "__main__":
     elif args.kv:
         main_kv(args.shapes or list(SHAPES), args.out, args.kv)
     else:
-        main(args.shapes or list(SHAPES), args.out)
+        main(args.shapes or list(SHAPES), args.out, args.steps)
