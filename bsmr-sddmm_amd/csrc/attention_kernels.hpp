@@ -29,7 +29,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "softmax_kernels.hpp"   // smWaveMax, smRowMax, smBlockMax, smExp, kSmChunk; spmm_kernels.hpp
+#include "softmax_device.hpp"    // attnDiv, smWaveMax, smRowMax, smExp
+#include "softmax_kernels.hpp"   // smBlockMax, kSmChunk; spmm_kernels.hpp
 
 namespace bsmr {
 
@@ -71,12 +72,6 @@ attnRowMax(const uint32_t* __restrict__ ro, const BwSplit* __restrict__ splits, 
     }
     mx = smRowMax(smWaveMax(mx), __any(nan));
     if (lane == 0) m[bM + r] = mx;
-}
-
-// O = acc / s as the contract defines it
-__device__ __forceinline__ float attnDiv(float acc, float s, bool dead) {
-#pragma clang fp contract(off)
-    return dead ? 0.0f : acc / s;
 }
 
 // Slice width W (floats) and lane layout as spmmGather.  p: the scores [b][nnz]; m: [b][M]; a direct item stores

@@ -48,7 +48,7 @@
 
 #include "attention_qkv_kernels.hpp"
 #include "attention_qkv_launch.hpp"   // BsmrAttnBlkRow
-#include "spmm_blocked_kernels.hpp"   // BlkPanel, BlkSegment, kBlkNull
+#include "blocked_format.hpp"         // BlkPanel, BlkSegment, kBlkNull
 
 namespace bsmr {
 

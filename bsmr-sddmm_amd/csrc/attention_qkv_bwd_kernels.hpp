@@ -43,7 +43,9 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "attention_kernels.hpp"   // smExp, smWaveSync; BwItem, BwSplit, kBwDirect, bwWiden, bwNarrow; ResidueLowp
+#include "backward_lists.hpp"   // BwItem, BwSplit, kBwDirect
+#include "lowp_device.hpp"      // u32x2, u32x4, ResidueLowp, bwWiden, bwNarrow
+#include "softmax_device.hpp"   // smExp, smWaveSync
 
 namespace bsmr {
 

@@ -37,7 +37,9 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "attention_kernels.hpp"   // attnDiv, smExp, smRowMax, smWaveSync; BwItem, BwSplit, bwWiden, bwNarrow; dot2
+#include "backward_lists.hpp"   // BwItem, BwSplit, kBwDirect
+#include "lowp_device.hpp"      // u32x2, u32x4, dot2, ResidueLowp, bwWiden, bwNarrow
+#include "softmax_device.hpp"   // attnDiv, smExp, smRowMax, smWaveSync
 
 namespace bsmr {
 

@@ -1,35 +1,16 @@
-// One-pass sparse attention on a quantised KV cache: the translation unit of attnQkvKv (csrc/attention_qkv_kv_kernels.hpp),
-// of this unit's attnQkvMerge, and their launches.  Like csrc/attention_qkv.hip it is built without packed fp32 operations
-// (Makefile, QKV_FLAGS; DESIGN.md 18 departure (4)), and it is a unit of its own so that its 90 instantiations compile
-// beside the 30 of attention_qkv.hip, not behind them.
-// For the reason given there - the nine non-template kernels of the shared kernel headers - the namespace of those headers
-// is renamed in this unit too, to a name of its own: bsmr_qkv_kv.
-#define bsmr bsmr_qkv_kv
-
+// One-pass sparse attention on a quantised KV cache: the translation unit of attnQkvKv (csrc/attention_qkv_kv_kernels.hpp)
+// and its launches; the merge of split rows is csrc/attention_qkv.hip's (bsmrLaunchAttnQkvMerge).  Like that unit it is built
+// without packed fp32 operations (Makefile, QKV_FLAGS; DESIGN.md 18 departure (4)), and it is a unit of its own so that its
+// 90 instantiations compile beside the 30 of attention_qkv.hip, not behind them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "bsmr_hip.h"
+#include "attention_qkv_dispatch.hpp"
 #include "attention_qkv_launch.hpp"
 #include "attention_qkv_kv_kernels.hpp"
 
 namespace {
-
-template <int N>
-using Int = std::integral_constant<int, N>;
-
-// fn(NL): the unroll class of the dot loop for K as a compile-time constant (attention_qkv.hip's classes)
-template <typename F>
-void withQkvPieces(uint32_t K, F&& fn) {
-    const uint32_t kc = K / 32u;
-    if (kc <= 1u) fn(Int<1>{});
-    else if (kc <= 2u) fn(Int<2>{});
-    else if (kc <= 4u) fn(Int<4>{});
-    else if (kc <= 8u) fn(Int<8>{});
-    else fn(Int<16>{});
-}
 
 struct QkvKvCall {
     const bsmr::BwItem* items;
@@ -50,7 +31,7 @@ template <int MODE, int FMT, bool MX>
 hipError_t launch(const QkvKvCall& c) {
     if (c.numItems) {
         const dim3 grid((c.numItems + 3u) / 4u, c.nb);
-        withQkvPieces(c.K, [&](auto NL) {
+        withPieces<16>(c.K / 32u, [&](auto NL) {   // the unroll class of the dot loop (attention_qkv.hip's classes)
             auto go = [&](auto VC) {
                 hipLaunchKernelGGL((bsmr::attnQkvKv<MODE, FMT, MX, NL(), VC()>), grid, dim3(256), 0, c.stream, c.items, c.numItems,
                                    c.src, c.scale, c.Q, c.Kt, c.Ks, c.V, c.Vs, c.O, c.m, c.s, c.partial, c.sPart, c.mPart, c.K,
@@ -63,14 +44,9 @@ hipError_t launch(const QkvKvCall& c) {
         });
         if (hipError_t e = hipGetLastError()) return e;
     }
-    if (c.numSplits) {   // only a handle with split rows launches the merge: fp32 partials, whatever the KV format
-        const uint64_t threads = (uint64_t)c.numSplits * (c.Kv / 4u);
-        const dim3 grid((uint32_t)((threads + 255u) / 256u), c.nb);
-        hipLaunchKernelGGL(bsmr::attnQkvMerge<MODE>, grid, dim3(256), 0, c.stream, c.splits, c.numSplits, c.partial, c.sPart,
-                           c.mPart, c.O, c.m, c.s, c.Kv, c.M, c.numSlots);
-        if (hipError_t e = hipGetLastError()) return e;
-    }
-    return hipSuccess;
+    // the merge of split rows: fp32 partials, whatever the KV format
+    return bsmrLaunchAttnQkvMerge(c.splits, c.numSplits, c.partial, c.sPart, c.mPart, c.O, c.m, c.s, c.Kv, c.M, c.numSlots, c.nb,
+                                  MODE == 1, c.stream);
 }
 
 template <int MODE>
@@ -82,13 +58,12 @@ hipError_t launchFormat(const QkvKvCall& c, int kvFormat, bool mx) {
 
 }  // namespace
 
-// (items / splits arrive untyped: bsmr_capi.hip's BwItem and this unit's are the same layout under two names)
-hipError_t bsmrLaunchAttnQkvKv(const void* items, uint32_t numItems, const void* splits, uint32_t numSplits, const uint32_t* src,
-                               float scale, const uint16_t* Q, const uint8_t* Kt, const uint8_t* Ks, const uint8_t* V,
-                               const uint8_t* Vs, uint16_t* O, float* m, float* s, float* partial, float* sPart, float* mPart,
-                               uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots, uint32_t numBatches, bool bf16,
-                               int kvFormat, bool mx, hipStream_t stream) {
-    const QkvKvCall c{static_cast<const bsmr::BwItem*>(items), numItems, static_cast<const bsmr::BwSplit*>(splits), numSplits, src,
-                      scale, Q, Kt, Ks, V, Vs, O, m, s, partial, sPart, mPart, K, Kv, M, N, numSlots, numBatches, stream};
+hipError_t bsmrLaunchAttnQkvKv(const bsmr::BwItem* items, uint32_t numItems, const bsmr::BwSplit* splits, uint32_t numSplits,
+                               const uint32_t* src, float scale, const uint16_t* Q, const uint8_t* Kt, const uint8_t* Ks,
+                               const uint8_t* V, const uint8_t* Vs, uint16_t* O, float* m, float* s, float* partial, float* sPart,
+                               float* mPart, uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots,
+                               uint32_t numBatches, bool bf16, int kvFormat, bool mx, hipStream_t stream) {
+    const QkvKvCall c{items, numItems, splits, numSplits, src, scale, Q, Kt, Ks, V, Vs, O, m, s, partial, sPart, mPart, K, Kv, M, N,
+                      numSlots, numBatches, stream};
     return bf16 ? launchFormat<1>(c, kvFormat, mx) : launchFormat<0>(c, kvFormat, mx);
 }

@@ -38,8 +38,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "attention_qkv_kernels.hpp"   // kQkvTile, attnQkvMerge; attnDiv, smExp, smRowMax, smWaveSync, BwItem, bwNarrow, dot2
-#include "fp4_kernels.hpp"             // bwWiden4; fp8_kernels.hpp behind it: bwWiden8, bwScaleMx
+#include "attention_qkv_kernels.hpp"   // kQkvTile; attnDiv, smExp, smRowMax, smWaveSync, BwItem, bwNarrow, dot2
+#include "quant_device.hpp"            // bwWiden8, bwWiden4, bwScaleMx
 
 namespace bsmr {
 

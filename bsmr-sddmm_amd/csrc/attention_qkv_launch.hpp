@@ -1,24 +1,34 @@
-// The one entry of csrc/attention_qkv.hip: the launches of attnQkv and attnQkvMerge (csrc/attention_qkv_kernels.hpp) for a
-// checked call.  items / splits: the handle's row-direction BwItem list and BwSplit table on the device (untyped here: the
-// kernel headers are private to that translation unit).  bf16: the 16-bit format, false = fp16.  Returns the launch status.
+// The entries of the one-pass attention units (csrc/attention_qkv*.hip), as bsmr_capi.hip calls them for a checked call.
+// The lists and the block format are the types of the helper headers, which both sides include: one definition, checked by
+// the compiler.  bf16: the 16-bit format, false = fp16.  Every entry returns the launch status.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-hipError_t bsmrLaunchAttnQkv(const void* items, uint32_t numItems, const void* splits, uint32_t numSplits, const uint32_t* src,
-                             float scale, const uint16_t* Q, const uint16_t* Kt, const uint16_t* V, uint16_t* O, float* m,
-                             float* s, float* partial, float* sPart, float* mPart, uint32_t K, uint32_t Kv, uint32_t M,
-                             uint32_t N, uint32_t numSlots, uint32_t numBatches, bool bf16, hipStream_t stream);
+#include "backward_lists.hpp"   // BwItem, BwSplit
+#include "blocked_format.hpp"   // BlkPanel, BlkSegment
+#include "lowp_device.hpp"      // u32x4
+
+// The entries of csrc/attention_qkv.hip.  bsmrLaunchAttnQkv: attnQkv over the handle's row-direction BwItem list, then the
+// merge of its BwSplit table.  bsmrLaunchAttnQkvMerge: attnQkvMerge (csrc/attention_qkv_kernels.hpp) alone, when there is a
+// split row; the unit of the quantised KV cache ends with it too, so the kernel has one home.
+hipError_t bsmrLaunchAttnQkv(const bsmr::BwItem* items, uint32_t numItems, const bsmr::BwSplit* splits, uint32_t numSplits,
+                             const uint32_t* src, float scale, const uint16_t* Q, const uint16_t* Kt, const uint16_t* V,
+                             uint16_t* O, float* m, float* s, float* partial, float* sPart, float* mPart, uint32_t K, uint32_t Kv,
+                             uint32_t M, uint32_t N, uint32_t numSlots, uint32_t numBatches, bool bf16, hipStream_t stream);
+hipError_t bsmrLaunchAttnQkvMerge(const bsmr::BwSplit* splits, uint32_t numSplits, const float* partial, const float* sPart,
+                                  const float* mPart, uint16_t* O, float* m, float* s, uint32_t Kv, uint32_t M,
+                                  uint32_t numSlots, uint32_t numBatches, bool bf16, hipStream_t stream);
 
 // The one entry of csrc/attention_qkv_bwd.hip: attnQkvBwdQ over the row direction's lists when dQ is asked for, attnQkvBwdKV
 // over the column direction's when dKt or dV is, each followed by attnQkvBwdReduce for its split destinations
 // (csrc/attention_qkv_bwd_kernels.hpp).  A gradient that is NULL is not computed.  D [b][M]: dO_r . O_r, already written on
 // the stream; rowPart [b][rows.numSlots][K] and colPart [b][cols.numSlots][K + Kv]: the chunk partials, written here.
 struct BsmrAttnBwdLists {   // one direction of the handle, on the device
-    const void* items;      // BwItem[numItems]
+    const bsmr::BwItem* items;     // [numItems]
     uint32_t numItems;
-    const void* splits;     // BwSplit[numSplits]
+    const bsmr::BwSplit* splits;   // [numSplits]
     uint32_t numSplits;
     const uint32_t* src;    // colIndices (rows) or cscRows (columns)
     uint32_t numSlots;
@@ -41,22 +51,24 @@ struct BsmrAttnBlkRow {
 };
 
 // The one entry of csrc/attention_qkv_blocked.hip: attnQkvBlocks over the RPHM's blocks, then attnQkvBlkMerge.  units:
-// BlkSegment[numUnits] if `segments`, else BlkPanel[numUnits]; cells / cols / panelRows / zeros: the device format of
-// bsmr_backward_attach_blocks; rows: BsmrAttnBlkRow[numRows].  partial / sPart / mPart [b][numSlots]: what attnQkv left for
-// the residue chunks; bPart [b][16 numUnits][Kv], bs and bm [b][16 numUnits]: the block partials, written here.
+// BlkSegment[numUnits] if `segments`, else BlkPanel[numUnits] (one of two types, so untyped); cells / cols / panelRows /
+// zeros: the device format of bsmr_backward_attach_blocks; rows: BsmrAttnBlkRow[numRows].  partial / sPart / mPart
+// [b][numSlots]: what attnQkv left for the residue chunks; bPart [b][16 numUnits][Kv], bs and bm [b][16 numUnits]: the block
+// partials, written here.
 hipError_t bsmrLaunchAttnQkvBlocks(const void* units, uint32_t numUnits, bool segments, const uint32_t* panelRows,
-                                   const void* cells, const void* cols, const float* zeros, const BsmrAttnBlkRow* rows,
-                                   uint32_t numRows, float scale, const uint16_t* Q, const uint16_t* Kt, const uint16_t* V,
-                                   uint16_t* O, float* m, float* s, const float* partial, const float* sPart,
-                                   const float* mPart, uint32_t numSlots, float* bPart, float* bs, float* bm, uint32_t K,
-                                   uint32_t Kv, uint32_t M, uint32_t N, uint32_t numBatches, bool bf16, hipStream_t stream);
+                                   const bsmr::u32x4* cells, const bsmr::u32x4* cols, const float* zeros,
+                                   const BsmrAttnBlkRow* rows, uint32_t numRows, float scale, const uint16_t* Q,
+                                   const uint16_t* Kt, const uint16_t* V, uint16_t* O, float* m, float* s, const float* partial,
+                                   const float* sPart, const float* mPart, uint32_t numSlots, float* bPart, float* bs, float* bm,
+                                   uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numBatches, bool bf16,
+                                   hipStream_t stream);
 
-// The one entry of csrc/attention_qkv_kv.hip: bsmrLaunchAttnQkv for attnQkvKv (csrc/attention_qkv_kv_kernels.hpp) and that unit's
-// attnQkvMerge.  Kt / V: the codes as the cache holds them; kvFormat: their format (the fp8 values are BSMR_FP8_E4M3 /
-// _E5M2); mx: Ks / Vs are the E8M0 block scales (always with e2m1), otherwise they are not read.
+// The one entry of csrc/attention_qkv_kv.hip: bsmrLaunchAttnQkv for attnQkvKv (csrc/attention_qkv_kv_kernels.hpp), ending in
+// bsmrLaunchAttnQkvMerge.  Kt / V: the codes as the cache holds them; kvFormat: their format (the fp8 values are
+// BSMR_FP8_E4M3 / _E5M2); mx: Ks / Vs are the E8M0 block scales (always with e2m1), otherwise they are not read.
 enum : int { kQkvKvE4M3 = 0, kQkvKvE5M2 = 1, kQkvKvE2M1 = 2 };
-hipError_t bsmrLaunchAttnQkvKv(const void* items, uint32_t numItems, const void* splits, uint32_t numSplits, const uint32_t* src,
-                               float scale, const uint16_t* Q, const uint8_t* Kt, const uint8_t* Ks, const uint8_t* V,
-                               const uint8_t* Vs, uint16_t* O, float* m, float* s, float* partial, float* sPart, float* mPart,
-                               uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots, uint32_t numBatches, bool bf16,
-                               int kvFormat, bool mx, hipStream_t stream);
+hipError_t bsmrLaunchAttnQkvKv(const bsmr::BwItem* items, uint32_t numItems, const bsmr::BwSplit* splits, uint32_t numSplits,
+                               const uint32_t* src, float scale, const uint16_t* Q, const uint8_t* Kt, const uint8_t* Ks,
+                               const uint8_t* V, const uint8_t* Vs, uint16_t* O, float* m, float* s, float* partial, float* sPart,
+                               float* mPart, uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots,
+                               uint32_t numBatches, bool bf16, int kvFormat, bool mx, hipStream_t stream);

@@ -26,28 +26,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fp8_kernels.hpp"   // bwScaleMx, bwScaleByte, bwStoreNarrow, bwStorePartial; bwBroadcast, attnDiv, smExp behind it
+#include "fp8_kernels.hpp"    // bwScaleByte, bwStoreNarrow, bwStorePartial; bwBroadcast, attnDiv, smExp behind it
+#include "quant_device.hpp"   // bwWiden4, bwScaleMx
 
 namespace bsmr {
-
-// The eight codes of a 32-bit word (element i in nibble i, the low nibble of a byte first), widened exactly to fp32:
-// v_cvt_scalef32_pk_f32_fp4 at scale 1.0 turns the two nibbles of one byte into two fp32 (-0 keeps its sign), op_sel
-// picks the byte.  The block scale is a separate fp32 multiplication (bwFma4Mx), as for fp8.
-__device__ __forceinline__ void bwWiden4(uint32_t word, float (&x)[8]) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    const f32x2 b0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, 1.0f, 0);
-    const f32x2 b1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, 1.0f, 1);
-    const f32x2 b2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, 1.0f, 2);
-    const f32x2 b3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, 1.0f, 3);
-    x[0] = b0[0];
-    x[1] = b0[1];
-    x[2] = b1[0];
-    x[3] = b1[1];
-    x[4] = b2[0];
-    x[5] = b2[1];
-    x[6] = b3[0];
-    x[7] = b3[1];
-}
 
 // The words one lane loads: VE source elements (8 -> one word, 16 -> u32x2, 32 -> u32x4)
 template <int VE> struct BwNibbles;

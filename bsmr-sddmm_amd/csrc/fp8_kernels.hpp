@@ -30,26 +30,9 @@
 #include <stdint.h>
 
 #include "attention_kernels.hpp"   // spmm_kernels.hpp: BwItem, BwWords, bwBroadcast, bwNarrow; attnDiv, smExp
+#include "quant_device.hpp"        // bwWiden8, bwScaleMx
 
 namespace bsmr {
-
-// The four codes of a 32-bit word (element i in byte i), widened exactly to fp32.
-template <int FMT>
-__device__ __forceinline__ void bwWiden8(uint32_t word, float (&x)[4]) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 lo, hi;
-    if constexpr (FMT == 0) {
-        lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)word, false);
-        hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)word, true);
-    } else {
-        lo = __builtin_amdgcn_cvt_pk_f32_bf8((int)word, false);
-        hi = __builtin_amdgcn_cvt_pk_f32_bf8((int)word, true);
-    }
-    x[0] = lo[0];
-    x[1] = lo[1];
-    x[2] = hi[0];
-    x[3] = hi[1];
-}
 
 // The words one lane loads: VE source bytes (8 -> u32x2, 16 -> u32x4)
 template <int VE> using BwBytes = typename BwWords<VE / 2>::T;
@@ -63,12 +46,6 @@ __device__ __forceinline__ void bwFma8(float w, const BwBytes<VE>& x, float (&ac
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[4 * i + k] = fmaf(w, e[k], acc[4 * i + k]);
     }
-}
-
-// 2^(e - 127) for an E8M0 code, built from bits: 1 .. 254 are the exponent field of a normal, 0 is the subnormal
-// 2^-127, 255 a quiet NaN
-__device__ __forceinline__ float bwScaleMx(uint32_t e) {
-    return __uint_as_float(e == 0u ? 0x00400000u : e == 255u ? 0x7FC00000u : e << 23);
 }
 
 // bwFma8 on dq = widen(code) * sc: the element is dequantised by one fp32 multiplication, then enters the chain

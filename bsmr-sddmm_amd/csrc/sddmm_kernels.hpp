@@ -43,13 +43,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace bsmr {
+#include "lowp_device.hpp"   // f32x4, u32x4, u32x3, f16x8, bf16x8; packLowp, dot2, ResidueLowp
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+namespace bsmr {
 
 constexpr int kWave = 64;
 constexpr int kThreads = 256;           // 4 waves per workgroup
@@ -87,21 +83,6 @@ __device__ __forceinline__ uint32_t xcdContiguous(uint32_t wg, uint32_t numWG) {
     const uint32_t xcd = wg & 7u, idx = wg >> 3;
     const uint32_t base = numWG >> 3, rem = numWG & 7u;  // XCD x owns base + (x < rem) items
     return xcd * base + (xcd < rem ? xcd : rem) + idx;
-}
-
-template <int MODE>
-__device__ __forceinline__ u32x4 packLowp(const f32x4& lo, const f32x4& hi) {
-    if constexpr (MODE == 0) {
-        f16x8 o;
-        o[0] = (_Float16)lo[0]; o[1] = (_Float16)lo[1]; o[2] = (_Float16)lo[2]; o[3] = (_Float16)lo[3];
-        o[4] = (_Float16)hi[0]; o[5] = (_Float16)hi[1]; o[6] = (_Float16)hi[2]; o[7] = (_Float16)hi[3];
-        return __builtin_bit_cast(u32x4, o);
-    } else {
-        bf16x8 o;
-        o[0] = (__bf16)lo[0]; o[1] = (__bf16)lo[1]; o[2] = (__bf16)lo[2]; o[3] = (__bf16)lo[3];
-        o[4] = (__bf16)hi[0]; o[5] = (__bf16)hi[1]; o[6] = (__bf16)hi[2]; o[7] = (__bf16)hi[3];
-        return __builtin_bit_cast(u32x4, o);
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -866,17 +847,6 @@ denseGroupsF32(const float* __restrict__ A, const float* __restrict__ B, uint32_
 // (sparseEntries<8, true, 4> takes 66 VGPRs with byte offsets, sparseEntriesLowp<8, MODE, true, 8> with element offsets).
 constexpr uint32_t kSparseLdsPad = 16;  // bytes per staged row: a row is K elements + the pad in both policies
 
-template <int MODE>
-__device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float acc) {
-    if constexpr (MODE == 0) {
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        return __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, a), __builtin_bit_cast(h2, b), acc, false);
-    } else {
-        typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-        return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(b2, a), __builtin_bit_cast(b2, b), acc, false);
-    }
-}
-
 struct ResidueF32 {
     typedef float elem;
     typedef f32x4 chunk;
@@ -889,21 +859,6 @@ struct ResidueF32 {
         acc = __builtin_fmaf(a[3], b[3], acc);
         return acc;
     }
-};
-template <int MODE>
-struct ResidueLowp {
-    typedef uint16_t elem;
-    typedef u32x4 chunk;
-    typedef uint8_t unit;
-    static constexpr uint32_t kPerChunk = 8;
-    static __device__ __forceinline__ float dot(const chunk& a, const chunk& b, float acc) {
-        acc = dot2<MODE>(a[0], b[0], acc);
-        acc = dot2<MODE>(a[1], b[1], acc);
-        acc = dot2<MODE>(a[2], b[2], acc);
-        acc = dot2<MODE>(a[3], b[3], acc);
-        return acc;
-    }
-    static __device__ __forceinline__ chunk round(const f32x4& lo, const f32x4& hi) { return packLowp<MODE>(lo, hi); }
 };
 
 // CPL > 0: K = kPerChunk * LPE * CPL, every lane's CPL column chunks are requested before the first

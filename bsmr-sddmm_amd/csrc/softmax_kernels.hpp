@@ -24,33 +24,13 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "softmax_device.hpp"   // smWaveMax, smWaveSync, smRowMax, smExp
 #include "spmm_kernels.hpp"
 
 namespace bsmr {
 
 constexpr uint32_t kSmChunk = BSMR_BACKWARD_CHUNK;
 constexpr uint32_t kSmPerLane = kSmChunk / 64u;   // entries of a short row held by one lane
-
-__device__ __forceinline__ float smWaveMax(float m) {
-    for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    return m;
-}
-
-// the wave's LDS writes before its own reads (rocPRIM's wave_barrier idiom; the short kernels' waves leave early, so
-// no block barrier there)
-__device__ __forceinline__ void smWaveSync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// m as the contract defines it: NaN if any z is NaN, else the max
-__device__ __forceinline__ float smRowMax(float m, bool nan) { return nan ? __int_as_float(0x7FC00000) : m; }
-
-__device__ __forceinline__ float smExp(float z, float m) {
-#pragma clang fp contract(off)
-    return m == -INFINITY ? 0.0f : expf(z - m);
-}
 
 // ---- rows of 1 .. kSmChunk entries: one wave per row, 4 rows per block ----
 __global__ void __launch_bounds__(256)

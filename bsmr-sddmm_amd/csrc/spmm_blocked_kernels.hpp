@@ -31,29 +31,10 @@
 // and of the partial area, nothing atomic.  With S = 0 the handle runs spmmBlocks[16], the panel form, as before.
 #pragma once
 
+#include "blocked_format.hpp"   // kBlkNull, BlkPanel, BlkSegment, BlkSplit
 #include "spmm_kernels.hpp"
 
 namespace bsmr {
-
-constexpr uint32_t kBlkNull = 0xFFFFFFFFu;   // an empty cell; a row of a ragged last panel that does not exist
-
-struct BlkPanel {          // a row panel that has blocks; its ordinal q owns rows [16 q, 16 q + 16) of the staging area
-    uint32_t firstBlock;
-    uint32_t numBlocks;
-};
-
-struct BlkSegment {        // S >= 1: `numBlocks` consecutive blocks of panel ordinal `panel`
-    uint32_t firstBlock;
-    uint32_t numBlocks;
-    uint32_t panel;
-    uint32_t partial;      // its slot (16 rows) of the partial area, or kBlkNull: the segment is the whole panel
-};
-
-struct BlkSplit {          // a panel cut into numSegments >= 2 segments, on the partial slots firstPartial ...
-    uint32_t panel;
-    uint32_t firstPartial;
-    uint32_t numSegments;
-};
 
 // MODE 2: fp32 rows (XT = float); 0 / 1: fp16 / bf16 rows (XT = uint16_t), widened exactly.  Four features of one row.
 template <int MODE, typename XT>

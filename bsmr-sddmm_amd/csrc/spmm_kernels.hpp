@@ -29,25 +29,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sddmm_kernels.hpp"   // u32x4; convertOperands (packLowp), the pass that rounds X
+#include "backward_lists.hpp"   // BwItem, BwSplit, kBwDirect
+#include "lowp_device.hpp"      // u32x2, u32x4, BwWords, bwWiden, bwNarrow
+#include "sddmm_kernels.hpp"    // convertOperands (packLowp), the pass that rounds X
 
 namespace bsmr {
-
-constexpr uint32_t kBwDirect = 0xFFFFFFFFu;   // BwItem.slot: the item owns its whole list and writes Y[dest]
-
-struct BwItem {
-    uint32_t dest;    // destination row of Y
-    uint32_t begin;   // [begin, end): positions in the direction's list array (CSR index or CSC position)
-    uint32_t end;
-    uint32_t slot;    // workspace row of this chunk's partial sum, or kBwDirect
-};
-
-struct BwSplit {      // a destination whose list was cut into numSlots chunks (partials at firstSlot ...)
-    uint32_t dest;
-    uint32_t firstSlot;
-    uint32_t numSlots;
-    uint32_t pad;
-};
 
 template <int V> struct BwVec;
 template <> struct BwVec<2> {
@@ -127,27 +113,6 @@ spmmGather(const BwItem* __restrict__ items, uint32_t numItems, uint32_t numSlic
     *reinterpret_cast<T*>(dst + (uint64_t)slice * W + (uint64_t)gl * V) = acc;
 }
 
-// The 16-bit words one lane loads (VE elements: 8 -> 16 bytes, 4 -> 8 bytes) and their exact widening to fp32.
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-template <int VE> struct BwWords;
-template <> struct BwWords<4> { using T = u32x2; };
-template <> struct BwWords<8> { using T = u32x4; };
-
-// MODE 0: two fp16 (v_cvt_f32_f16 keeps fp16 subnormals, inf and NaN); MODE 1: two bf16 (the upper half of an fp32).
-// Element 2i is the low half of word i.
-template <int MODE>
-__device__ __forceinline__ void bwWiden(uint32_t pair, float& lo, float& hi) {
-    if constexpr (MODE == 0) {
-        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-        const f16x2 h = __builtin_bit_cast(f16x2, pair);
-        lo = (float)h[0];
-        hi = (float)h[1];
-    } else {
-        lo = __uint_as_float(pair << 16);
-        hi = __uint_as_float(pair & 0xFFFF0000u);
-    }
-}
-
 template <int MODE, int VE>
 __device__ __forceinline__ void bwFma16(float w, const typename BwWords<VE>::T& x, float (&acc)[VE]) {
 #pragma unroll
@@ -156,25 +121,6 @@ __device__ __forceinline__ void bwFma16(float w, const typename BwWords<VE>::T& 
         bwWiden<MODE>(x[i], lo, hi);
         acc[2 * i] = fmaf(w, lo, acc[2 * i]);
         acc[2 * i + 1] = fmaf(w, hi, acc[2 * i + 1]);
-    }
-}
-
-// Two fp32 sums rounded to MODE's format (round to nearest even, fp16 subnormals kept, +-inf beyond the range, NaN stays
-// NaN: the casts of packLowp), element 2i in the low half of word i - the inverse of bwWiden.
-template <int MODE>
-__device__ __forceinline__ uint32_t bwNarrow(float lo, float hi) {
-    if constexpr (MODE == 0) {
-        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-        f16x2 o;
-        o[0] = (_Float16)lo;
-        o[1] = (_Float16)hi;
-        return __builtin_bit_cast(uint32_t, o);
-    } else {
-        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-        bf16x2 o;
-        o[0] = (__bf16)lo;
-        o[1] = (__bf16)hi;
-        return __builtin_bit_cast(uint32_t, o);
     }
 }
 
