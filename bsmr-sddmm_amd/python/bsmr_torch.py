@@ -125,6 +125,7 @@ _SCALE_DTYPES = (torch.uint8,) + ((torch.float8_e8m0fnu,) if hasattr(torch, "flo
 MX_BLOCK = 32
 ONE_PASS_MAX_K = 512   # attention(one_pass=True): one wave holds a whole row of Q (K) and of the accumulators (Kv)
 ONE_PASS_BACKWARD_MAX_K = 256   # ... with one_pass_backward=True: a lane of the column side holds (K + Kv) / 4 accumulators
+ONE_PASS_GROUPED_MAX_K = 256    # ... with grouped key/value heads: one wave holds up to 8 rows of Q and of acc
 _FP4 = getattr(torch, "float4_e2m1fn_x2", None)   # two e2m1 codes per byte, element 2i in the low nibble
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # the magnitude of code 0 .. 7; bit 3 is the sign
 _E2M1_TIES = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)   # the midpoint between codes i and i + 1
@@ -326,7 +327,14 @@ class SparseOperator:
         one_pass_backward=True (with one_pass=True, 16-bit Kt and V, blocks=False, K and Kv at most 256): the backward is one
         call as well (bsmr_sparse_attention_qkv_backward_16) - dQ, dKt and dV from Q, Kt, V, O, dO and the saved (m, s) with
         scores and weights in registers only, nothing of size nnz in the whole step.  The same gradients in another
-        summation order.  The default False keeps every path and bit."""
+        summation order.  The default False keeps every path and bit.
+        Grouped key/value heads (GQA / MQA; one_pass=True, 3-D operands): Kt (bk, N, K) and V (bk, N, Kv) with bk < b and
+        b % bk == 0 - query head h reads KV head h // (b / bk), the repeat_interleave convention - run one kernel that
+        reads each row of Kt and V once per group (bsmr_sparse_attention_qkv_gqa_16): the bits of one_pass=True on
+        repeat_interleaved Kt and V.  16-bit Kt and V, K and Kv at most 256, blocks=False.  There is no grouped backward
+        kernel: the backward repeats the 16-bit Kt and V (b N (K + Kv) elements, nothing of size nnz), runs one_pass=True's
+        backward (one_pass_backward is honoured), sums dKt and dV over each group in fp32 and rounds once."""
+        group = self._check_grouped(Q, Kt, V, blocks) if one_pass else None
         if one_pass_backward:
             self._check_one_pass_backward(Q, Kt, V, one_pass, blocks)
         if blocks:
@@ -336,6 +344,11 @@ class SparseOperator:
                 raise ValueError("fused=True with one_pass=True: they are two different paths, choose one")
             quantised, Kts, Vs = self._check_one_pass(Q, Kt, V, out_dtype, Kt_scale, V_scale)
             scale = Q.shape[-1] ** -0.5 if scale is None else scale
+            if group is not None:
+                if quantised:
+                    raise ValueError(f"Kt: dtype {Kt.dtype} with grouped key/value heads - the grouped form takes "
+                                     "torch.float16 or torch.bfloat16 keys and values")
+                return _AttentionOnePassGqa.apply(self, Q, Kt, V, scale, group, one_pass_backward)
             if quantised:
                 return _AttentionOnePassKv.apply(self, Q, Kt, V, scale, Kts, Vs)
             if blocks:
@@ -670,6 +683,31 @@ class SparseOperator:
                              "without; one scaled operand beside an unscaled one goes through one_pass=False")
         return True, self._check_scale(Kt_scale, "Kt_scale", Kt), self._check_scale(V_scale, "V_scale", V)
 
+    @staticmethod
+    def _check_grouped(Q, Kt, V, blocks):
+        """g = b / bk when attention(one_pass=True) is called with grouped key/value heads, None when it is not; the limits
+        of the grouped form, named before any device work"""
+        if not all(isinstance(t, torch.Tensor) and t.dim() == 3 for t in (Q, Kt, V)):
+            return None
+        b, bk = Q.shape[0], Kt.shape[0]
+        if bk == b and V.shape[0] == b:
+            return None
+        if V.shape[0] != bk:
+            raise ValueError(f"Kt has {bk} heads and V {V.shape[0]}: grouped keys and values share their leading size")
+        if bk == 0 or bk > b or b % bk:
+            raise ValueError(f"Kt, V: {bk} key/value heads do not divide the {b} heads of Q")
+        if blocks:
+            raise ValueError("blocks=True with grouped key/value heads: the blocked form has no grouped kernel")
+        for t, name in ((Kt, "Kt"), (V, "V")):
+            if _is8(t) or _is4(t):
+                raise ValueError(f"{name}: dtype {t.dtype} with grouped key/value heads - the grouped form takes "
+                                 "torch.float16 or torch.bfloat16 keys and values")
+        for t, name in ((Q, "Q"), (Kt, "Kt"), (V, "V")):
+            if t.shape[-1] > ONE_PASS_GROUPED_MAX_K:
+                raise ValueError(f"{name}: {t.shape[-1]} features - grouped key/value heads take K and Kv in "
+                                 f"32 ... {ONE_PASS_GROUPED_MAX_K}")
+        return b // bk
+
     def _check_one_pass_backward(self, Q, Kt, V, one_pass, blocks):
         """the limits attention(one_pass_backward=True) adds to one_pass=True's, named before any device work"""
         if not one_pass:
@@ -721,6 +759,26 @@ class SparseOperator:
         call = eng.sparse_attention_qkv_blocked_16 if blocks else eng.sparse_attention_qkv_16
         call(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(), m.data_ptr(), s.data_ptr(), b or 1,
              self._stream(), mode=_MODE16[Q.dtype])
+        return O, m, s
+
+    def _attention_qkv_gqa(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, group: int):
+        """_attention_qkv with grouped key/value heads: Q (b, M, K), Kt (b / group, N, K), V (b / group, N, Kv)"""
+        b, K = self._check(Q, "Q", self.M, None)
+        _, K2 = self._check(Kt, "Kt", self.N, (b // group,))
+        _, Kv = self._check(V, "V", self.N, (b // group,))
+        if K2 != K:
+            raise ValueError(f"Q and Kt disagree on K ({K} vs {K2})")
+        try:
+            scale = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"scale: {scale!r} is not a number") from None
+        if not math.isfinite(scale):
+            raise ValueError(f"scale: {scale} is not finite")
+        O = torch.empty((b, self.M, Kv), dtype=Q.dtype, device=self.device)
+        m = torch.empty((b, self.M), dtype=torch.float32, device=self.device)
+        s = torch.empty_like(m)
+        eng.sparse_attention_qkv_gqa_16(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(),
+                                        m.data_ptr(), s.data_ptr(), b, group, self._stream(), mode=_MODE16[Q.dtype])
         return O, m, s
 
     def _attention_qkv_kv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, Kts=None, Vs=None):
@@ -1026,6 +1084,38 @@ class _AttentionOnePassBwd(_AttentionOnePass):
         Q, Kt, V, O, m, s = ctx.saved_tensors
         dQ, dKt, dV = ctx.op._attention_qkv_backward(Q, Kt, V, O, _grad(dO, O.dtype), m, s, ctx.scale, need_q, need_k, need_v)
         return None, dQ, dKt, dV, None
+
+
+class _AttentionOnePassGqa(torch.autograd.Function):
+    """attention(one_pass=True) with grouped key/value heads (group = query heads per KV head): the forward is one grouped
+    call; there is no grouped backward kernel, so the backward is _AttentionOnePass's (or _AttentionOnePassBwd's) on the
+    repeated 16-bit Kt and V, with dKt and dV summed over each group in fp32 and rounded once"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, Q, Kt, V, scale, group, one_pass_backward):
+        O, m, s = op._attention_qkv_gqa(Q, Kt, V, scale, group)
+        ctx.op, ctx.scale, ctx.group, ctx.one_pass_backward = op, float(scale), group, one_pass_backward
+        ctx.save_for_backward(Q, Kt, V, O, m, s)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        op, g = ctx.op, ctx.group
+        need_q, need_k, need_v = ctx.needs_input_grad[1:4]
+        if not (need_q or need_k or need_v):
+            return (None,) * 7
+        Q, Kt, V, O, m, s = ctx.saved_tensors
+        Kr, Vr = Kt.repeat_interleave(g, 0), V.repeat_interleave(g, 0)   # b N (K + Kv) elements: nothing of size nnz
+        dO = _grad(dO, O.dtype)
+        if ctx.one_pass_backward:
+            dQ, dKr, dVr = op._attention_qkv_backward(Q, Kr, Vr, O, dO, m, s, ctx.scale, need_q, need_k, need_v)
+        else:
+            P = op._sddmm(Q, Kr)   # the scores exist only from here on
+            dP, W = op._attention_backward(P, m, s, op._sddmm(dO, Vr), O, dO, ctx.scale)
+            dVr = op._spmm(W, dO, True) if need_v else None
+            dQ, dKr = op._sddmm_backward(dP, Q, Kr, need_q, need_k) if need_q or need_k else (None, None)
+        fold = lambda d, t: None if d is None else d.view((-1, g) + d.shape[1:]).sum(1, dtype=torch.float32).to(t.dtype)
+        return None, dQ, fold(dKr, Kt), fold(dVr, V), None, None, None
 
 
 class _AttentionOnePassBlocks(_AttentionOnePass):

@@ -929,6 +929,27 @@ int bsmr_sparse_attention_qkv_backward_16(bsmr_backward *bw, uint32_t K, uint32_
                                           void *dKt16_dev, void *dV16_dev, uint32_t num_batches, int compute_mode,
                                           void *stream);
 
+/* ---- One-pass sparse attention with grouped key/value heads, GQA / MQA (revision 5, added without any layout change) ----
+ * bsmr_sparse_attention_qkv_16 for models whose query heads share key/value heads: Q [b][M][K], O [b][M][Kv], m and s
+ * [b][M] have num_batches = b query heads; Kt [b/g][N][K] and V [b/g][N][Kv] have b / g heads, g = kv_group, in Q's 16-bit
+ * format.  Query head h reads KV head h / g: consecutive heads share a KV head, the repeat_interleave convention.  The g
+ * heads of a KV group walk S's entries in the same order, so one wave serves up to 8 of them and reads each row of Kt and
+ * of V and each column id once for all of them; nothing is repeated in memory.
+ * Contract: every head runs the statement sequence of "One-pass sparse attention" on the same values, so O, m and s are
+ * bit for bit those of bsmr_sparse_attention_qkv_16 on Kt and V repeated g times along the head axis - empty rows, -inf
+ * rows (the skip while m = -inf is kept per head), NaN propagation and split rows included.  That section's exact cases,
+ * reproducibility and forward bound hold unchanged.
+ * Limits: K and Kv multiples of 32 in 32 ... 256 when kv_group > 1.  kv_group = 1 is bsmr_sparse_attention_qkv_16 itself
+ * (the same kernel and bits, K and Kv up to 512).
+ * Workspace: that of bsmr_sparse_attention_qkv_16, indexed by query head; bsmr_sparse_attention_qkv_reserve(K, Kv,
+ * num_batches) sizes it.
+ * Checked before any device call, in this order: a NULL handle or a non-finite scale, kv_group = 0 or not a divisor of
+ * num_batches (BSMR_ERR_INVALID_ARG), K or Kv (BSMR_ERR_UNSUPPORTED_K), then compute_mode, the batches and the pointers as
+ * bsmr_sparse_attention_qkv_16.  num_batches = 0 is a no-op.  With nnz = 0 the inputs may be NULL. */
+int bsmr_sparse_attention_qkv_gqa_16(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                     const void *Kt16_dev, const void *V16_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                     uint32_t num_batches, uint32_t kv_group, int compute_mode, void *stream);
+
 /* ---- fp8 keys and values (revision 5, added without any layout change; no reference counterpart) ----
  * The column-side operand - B / Kt of the SDDMM, X / V of the SpMM and of the fused attention - may be OCP fp8, one byte per
  * element, as an fp8 KV cache holds it: fp8_format BSMR_FP8_E4M3 (e4m3fn: no infinity, two NaN codes) or BSMR_FP8_E5M2 (two

@@ -21,7 +21,11 @@ attached whole (segment_blocks 0) and in segments of S blocks: the fused path, t
 call (bsmr_sparse_attention_qkv_blocked_16) side by side in one job, K = Kv = 128, b = 1 and 8, fp16 and bf16.  coverage
 is the blocks' entries / nnz: what the blocked kernel serves; the rest is the residue on the one-pass gather.
 --steps: only the 16-bit step and peak columns of the first form (fused, one-pass, one-pass with its own backward).
-Usage: python tools/attention_lab.py [--steps | --kv FORMAT | --blocks S] [--out FILE] [shape ...]   (one JSON line per shape)"""
+--kv-group G [--features K]: instead of the above, the 16-bit forward with G query heads per key/value head, 1 and 2 KV
+heads (b = G and 2 G), K = Kv = 128 or --features: the repeat_interleave of Kt and V on its own, the fused path and the
+one-pass call on the repeated operands, and the grouped call (bsmr_sparse_attention_qkv_gqa_16) on the operands as they are.
+Usage: python tools/attention_lab.py [--steps | --kv FORMAT | --blocks S | --kv-group G] [--out FILE] [shape ...]
+(one JSON line per shape)"""
 import argparse
 import json
 import sys
@@ -220,8 +224,49 @@ def main_blocks(names, out, S):
         torch.cuda.empty_cache()
 
 
+def main_gqa(names, out, g, Kw):
+    for name in names:
+        gen, kwargs, _ = SHAPES[name]
+        rows, cols, ro, ci = getattr(synth, gen)(**kwargs)
+        ro = np.ascontiguousarray(ro, dtype=np.uint32)
+        ci = np.ascontiguousarray(ci, dtype=np.uint32)
+        scale = Kw ** -0.5
+        op = bsmr_torch.SparseOperator(eng.CSR.from_arrays(rows, cols, ro, ci), device=0)
+        line = {"shape": name, "M": rows, "N": cols, "nnz": int(ci.size), "K": Kw, "kv_group": g}
+        us = {}
+        for bk in (1, 2):
+            b = bk * g
+            eng.sparse_attention_reserve(op._bw, Kw, b)
+            eng.sparse_attention_qkv_reserve(op._bw, Kw, Kw, b)
+            for dtype, tag in ((torch.float16, "f16"), (torch.bfloat16, "bf16")):
+                gen_ = torch.Generator(device=dev).manual_seed(7)
+                Q, Kt, V = (torch.randn(h, n, Kw, device=dev, generator=gen_).to(dtype) for h, n in ((b, rows), (bk, cols), (bk, cols)))
+                key = f"kv{bk}_{tag}"
+                us[f"repeat_{key}"] = windows(lambda: (Kt.repeat_interleave(g, 0), V.repeat_interleave(g, 0)))
+                Kr, Vr = Kt.repeat_interleave(g, 0), V.repeat_interleave(g, 0)
+                us[f"fwd_fused_{key}"] = windows(lambda: op._attention(op._sddmm(Q, Kr), Vr, scale))
+                us[f"fwd_one_pass_{key}"] = windows(lambda: op._attention_qkv(Q, Kr, Vr, scale))
+                us[f"fwd_grouped_{key}"] = windows(lambda: op._attention_qkv_gqa(Q, Kt, V, scale, g))
+                same = all(torch.equal(x.view(torch.int32 if x.dtype == torch.float32 else torch.int16),
+                                       y.view(torch.int32 if y.dtype == torch.float32 else torch.int16))
+                           for x, y in zip(op._attention_qkv_gqa(Q, Kt, V, scale, g), op._attention_qkv(Q, Kr, Vr, scale)))
+                line[f"same_bits_{key}"] = same
+                del Q, Kt, V, Kr, Vr
+        line["us"] = us
+        text = json.dumps(line)
+        print(text, flush=True)
+        if out:
+            with open(out, "a") as f:
+                f.write(text + "\n")
+        del op
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kv-group", type=int, default=None, metavar="G",
+                    help="time the grouped one-pass forward (G query heads per KV head) beside one-pass and fused on repeated Kt / V")
+    ap.add_argument("--features", type=int, default=128, metavar="K", help="K = Kv of --kv-group (default 128)")
     ap.add_argument("--kv", choices=("fp8", "mxfp8", "mxfp4"), default=None,
                     help="time the forward on a quantised KV cache: fused path against one-pass")
     ap.add_argument("--blocks", type=int, default=None, metavar="S",
@@ -233,7 +278,11 @@ if __name__ == "__main__":
     unknown = [n for n in args.shapes if n not in SHAPES]
     if unknown:
         ap.error(f"unknown shape(s) {unknown}")
-    if args.blocks is not None:
+    if args.kv_group is not None:
+        if args.kv or args.blocks is not None or args.kv_group < 2 or args.features % 32 or not 32 <= args.features <= 256:
+            ap.error("--kv-group takes G >= 2, K = Kv a multiple of 32 up to 256, and excludes --kv and --blocks")
+        main_gqa(args.shapes or list(SHAPES), args.out, args.kv_group, args.features)
+    elif args.blocks is not None:
         if args.kv or args.blocks < 1:
             ap.error("--blocks takes S >= 1 and excludes --kv")
         main_blocks(args.shapes or list(SHAPES), args.out, args.blocks)
