@@ -1,5 +1,6 @@
 // One-pass backward of sparse attention: the translation unit of attnQkvBwdQ / attnQkvBwdKV / attnQkvBwdReduce
-// (csrc/attention_qkv_bwd_kernels.hpp) and their launches.  Built like csrc/attention_qkv.hip: without packed fp32
+// (csrc/attention_qkv_bwd_kernels.hpp) and their launches; attnQkvBwdReduce has its home here, and the unit of the grouped
+// backward ends with it too (bsmrLaunchAttnQkvBwdReduce).  Built like csrc/attention_qkv.hip: without packed fp32
 // operations (Makefile, QKV_FLAGS), on helper headers that define no kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,4 +73,27 @@ hipError_t bsmrLaunchAttnQkvBwd(const BsmrAttnBwdLists& rows, const BsmrAttnBwdL
                                 hipStream_t stream) {
     const QkvBwdCall c{rows, cols, scale, Q, Kt, V, dO, m, s, D, dQ, dKt, dV, rowPart, colPart, K, Kv, M, N, numBatches, stream};
     return bf16 ? launch<1>(c) : launch<0>(c);
+}
+
+// The reduce alone, for the unit of the grouped backward.  launch() above keeps its own launch statement, and this entry
+// reaches the kernel through a template of its own: the compiler emits a unit's kernels in the order in which they are
+// first instantiated, and the unit's assembly is compared byte for byte with its earlier one.
+namespace {
+template <int MODE>
+hipError_t launchReduce(const BsmrAttnBwdLists& L, const float* partial, uint32_t stride, uint32_t offset, uint16_t* out,
+                        uint32_t width, uint32_t outRows, uint32_t nb, hipStream_t stream) {
+    const uint64_t threads = (uint64_t)L.numSplits * (width / 4u);
+    const dim3 grid((uint32_t)((threads + 255u) / 256u), nb);
+    hipLaunchKernelGGL(bsmr::attnQkvBwdReduce<MODE>, grid, dim3(256), 0, stream, L.splits, L.numSplits, partial, stride, offset, out,
+                       width, outRows, L.numSlots);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t bsmrLaunchAttnQkvBwdReduce(const BsmrAttnBwdLists& lists, const float* partial, uint32_t stride, uint32_t offset,
+                                      uint16_t* out, uint32_t width, uint32_t outRows, uint32_t numBatches, bool bf16,
+                                      hipStream_t stream) {
+    if (!lists.numSplits) return hipSuccess;   // only a direction with split destinations launches the reduce
+    return bf16 ? launchReduce<1>(lists, partial, stride, offset, out, width, outRows, numBatches, stream)
+                : launchReduce<0>(lists, partial, stride, offset, out, width, outRows, numBatches, stream);
 }

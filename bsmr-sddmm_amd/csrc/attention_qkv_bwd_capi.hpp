@@ -26,6 +26,18 @@ uint64_t qkvBwdWorkFloats(const bsmr_backward* bw, uint32_t K, uint32_t Kv, uint
     return qkvBwdPartFloats(bw, K, Kv, nb) + (uint64_t)bw->M * nb;
 }
 
+// D [nb][M] = dO_r . O_r of every row, by attnRowDot; the grouped backward (attention_qkv_gqa_bwd_capi.hpp) starts with it too
+int launchQkvBwdRowDot(const bsmr_backward* bw, const uint16_t* O, const uint16_t* dO, float* D, uint32_t Kv, uint32_t nb, int mode,
+                       hipStream_t s) {
+    const uint64_t rows = (uint64_t)bw->M * nb;
+    if (bw->nnz && rows) {   // (without entries no kernel reads D, and O / dO may be NULL)
+        const dim3 dgrid((uint32_t)((rows + 7u) / 8u));
+        withMode(mode, [&](auto MODE) { hipLaunchKernelGGL(bsmr::attnRowDot<MODE()>, dgrid, dim3(256), 0, s, O, dO, D, rows, Kv); });
+        BSMR_HIP(hipGetLastError());
+    }
+    return BSMR_OK;
+}
+
 int runAttentionQkvBwd(bsmr_backward* bw, uint32_t K, uint32_t Kv, float scale, const uint16_t* Q, const uint16_t* Kt,
                        const uint16_t* V, const uint16_t* O, const uint16_t* dO, const float* m, const float* sIn, uint16_t* dQ,
                        uint16_t* dKt, uint16_t* dV, uint32_t nb, int mode, hipStream_t s) {
@@ -33,12 +45,7 @@ int runAttentionQkvBwd(bsmr_backward* bw, uint32_t K, uint32_t Kv, float scale, 
     float* rowPart = bw->work;
     float* colPart = rowPart + (uint64_t)bw->numSlots[0] * K * nb;
     float* D = bw->work + qkvBwdPartFloats(bw, K, Kv, nb);
-    const uint64_t rows = (uint64_t)bw->M * nb;
-    if (bw->nnz && rows) {   // (without entries no kernel reads D, and O / dO may be NULL)
-        const dim3 dgrid((uint32_t)((rows + 7u) / 8u));
-        withMode(mode, [&](auto MODE) { hipLaunchKernelGGL(bsmr::attnRowDot<MODE()>, dgrid, dim3(256), 0, s, O, dO, D, rows, Kv); });
-        BSMR_HIP(hipGetLastError());
-    }
+    if (int st = launchQkvBwdRowDot(bw, O, dO, D, Kv, nb, mode, s)) return st;
     const BsmrAttnBwdLists rowLists{bw->items[0].get(), bw->numItems[0], bw->splits[0].get(), bw->numSplits[0], bw->colIndices,
                                     bw->numSlots[0]};
     const BsmrAttnBwdLists colLists{bw->items[1].get(), bw->numItems[1], bw->splits[1].get(), bw->numSplits[1], bw->cscRows,

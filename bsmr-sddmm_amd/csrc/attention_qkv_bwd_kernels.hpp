@@ -86,9 +86,10 @@ __device__ __forceinline__ void bwdLoadTile(const uint16_t* row, uint32_t pc, u3
 }
 
 // The dot of the item's row with this lane's entry's row, the same bits on the entry's four lanes.  FIRST: the item's
-// row is the first operand of dot2 (the row side: Q_r, dO_r), otherwise the gathered one is (the column side).
-template <int MODE, bool FIRST, int NP>
-__device__ __forceinline__ float bwdQuadDot(const BwdRow<NP>& own, const u32x4 (&x)[NP], uint32_t pc, uint32_t quarter) {
+// row is the first operand of dot2 (the row side: Q_r, dO_r), otherwise the gathered one is (the column side).  Own: a
+// BwdRow<NP>, or any row with its piece(i, pc, quarter).
+template <int MODE, bool FIRST, int NP, typename Own>
+__device__ __forceinline__ float bwdQuadDot(const Own& own, const u32x4 (&x)[NP], uint32_t pc, uint32_t quarter) {
 #pragma clang fp contract(off)
     float p = 0.0f;
 #pragma unroll

@@ -48,6 +48,22 @@ hipError_t bsmrLaunchAttnQkvBwd(const BsmrAttnBwdLists& rows, const BsmrAttnBwdL
                                 const float* D, uint16_t* dQ, uint16_t* dKt, uint16_t* dV, float* rowPart, float* colPart,
                                 uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numBatches, bool bf16,
                                 hipStream_t stream);
+// bsmrLaunchAttnQkvBwdReduce: attnQkvBwdReduce alone, when `lists` has a split destination; the unit of the grouped backward
+// ends with it too, so the kernel has one home.  A slot's row of `partial` [numBatches][lists.numSlots] is `stride` floats,
+// the gradient's `width` floats lie at `offset` in it; out [numBatches][outRows][width].
+hipError_t bsmrLaunchAttnQkvBwdReduce(const BsmrAttnBwdLists& lists, const float* partial, uint32_t stride, uint32_t offset,
+                                      uint16_t* out, uint32_t width, uint32_t outRows, uint32_t numBatches, bool bf16,
+                                      hipStream_t stream);
+
+// The one entry of csrc/attention_qkv_gqa_bwd.hip: bsmrLaunchAttnQkvBwd for grouped key/value heads - attnQkvGqaBwdQ and
+// attnQkvGqaBwdKV (csrc/attention_qkv_gqa_bwd_kernels.hpp), each followed by bsmrLaunchAttnQkvBwdReduce.  Q, dO, m, s, D, dQ
+// and rowPart have numBatches query heads; Kt, V, dKt, dV and colPart [b / g][cols.numSlots][K + Kv] numBatches / kvGroup
+// heads; query head h reads KV head h / kvGroup.  kvGroup >= 2 divides numBatches (the caller checked).
+hipError_t bsmrLaunchAttnQkvGqaBwd(const BsmrAttnBwdLists& rows, const BsmrAttnBwdLists& cols, float scale, const uint16_t* Q,
+                                   const uint16_t* Kt, const uint16_t* V, const uint16_t* dO, const float* m, const float* s,
+                                   const float* D, uint16_t* dQ, uint16_t* dKt, uint16_t* dV, float* rowPart, float* colPart,
+                                   uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numBatches, uint32_t kvGroup,
+                                   bool bf16, hipStream_t stream);
 
 // A row of a panel with blocks, as attnQkvBlkMerge (csrc/attention_qkv_blocked_kernels.hpp) merges it: its residue chunks
 // on the slots resFirst ... of attnQkv's partial area, then its block units on the rows blkFirst, blkFirst + 16, ... of

@@ -271,6 +271,8 @@ HIP_SYMBOLS = {
                                               [C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_qkv_gqa_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
                                          [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_gqa_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 10 +
+                                                  [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_widen_fp8": (C.c_int,[C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
     "bsmr_sddmm_b8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int,
                                 C.c_void_p]),
@@ -1024,6 +1026,18 @@ def sparse_attention_qkv_backward_16(bw, K: int, Kv: int, scale: float, Q_ptr: i
                                                        O_ptr or None, dO_ptr or None, m_ptr or None, s_ptr or None,
                                                        dQ_ptr or None, dKt_ptr or None, dV_ptr or None, num_batches, mode,
                                                        stream), "bsmr_sparse_attention_qkv_backward_16")
+
+
+def sparse_attention_qkv_gqa_backward_16(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt_ptr: int, V_ptr: int, O_ptr: int,
+                                         dO_ptr: int, m_ptr: int, s_ptr: int, dQ_ptr: int, dKt_ptr: int, dV_ptr: int,
+                                         num_batches: int = 1, kv_group: int = 1, stream: int = 0, mode=COMPUTE_F16):
+    """sparse_attention_qkv_backward_16 with grouped key/value heads: Q, O, dO, m, s, dQ have num_batches query heads, Kt, V,
+    dKt, dV num_batches / kv_group; query head h reads KV head h // kv_group.  dQ has the bits of the ungrouped call on
+    repeat_interleaved Kt and V; dKt and dV are rounded once from the fp32 sum over the group"""
+    _check(hip().bsmr_sparse_attention_qkv_gqa_backward_16(bw, K, Kv, scale, Q_ptr or None, Kt_ptr or None, V_ptr or None,
+                                                           O_ptr or None, dO_ptr or None, m_ptr or None, s_ptr or None,
+                                                           dQ_ptr or None, dKt_ptr or None, dV_ptr or None, num_batches, kv_group,
+                                                           mode, stream), "bsmr_sparse_attention_qkv_gqa_backward_16")
 
 
 # --- fp8 keys and values: the column-side operand as OCP fp8 bytes (fmt FP8_E4M3 / FP8_E5M2), widened exactly to the

@@ -331,9 +331,12 @@ class SparseOperator:
         Grouped key/value heads (GQA / MQA; one_pass=True, 3-D operands): Kt (bk, N, K) and V (bk, N, Kv) with bk < b and
         b % bk == 0 - query head h reads KV head h // (b / bk), the repeat_interleave convention - run one kernel that
         reads each row of Kt and V once per group (bsmr_sparse_attention_qkv_gqa_16): the bits of one_pass=True on
-        repeat_interleaved Kt and V.  16-bit Kt and V, K and Kv at most 256, blocks=False.  There is no grouped backward
-        kernel: the backward repeats the 16-bit Kt and V (b N (K + Kv) elements, nothing of size nnz), runs one_pass=True's
-        backward (one_pass_backward is honoured), sums dKt and dV over each group in fp32 and rounds once."""
+        repeat_interleaved Kt and V.  16-bit Kt and V, K and Kv at most 256, blocks=False.  With one_pass_backward=True the
+        backward is one grouped call too (bsmr_sparse_attention_qkv_gqa_backward_16) on the operands as they are: dQ has the
+        bits of one_pass_backward=True on repeat_interleaved Kt and V, dKt and dV come out per KV head, each rounded once from
+        an fp32 sum over the whole group - nothing is repeated and nothing is folded.  With the default False the backward
+        repeats the 16-bit Kt and V (b N (K + Kv) elements, nothing of size nnz), runs one_pass=True's backward, sums dKt and
+        dV over each group in fp32 and rounds once."""
         group = self._check_grouped(Q, Kt, V, blocks) if one_pass else None
         if one_pass_backward:
             self._check_one_pass_backward(Q, Kt, V, one_pass, blocks)
@@ -810,12 +813,14 @@ class SparseOperator:
                                          mode=_MODE16[Q.dtype], fmt=_MODE8[Kt.dtype])
         return O, m, s
 
-    def _attention_qkv_backward(self, Q, Kt, V, O, dO, m, s, scale, need_q=True, need_k=True, need_v=True):
+    def _attention_qkv_backward(self, Q, Kt, V, O, dO, m, s, scale, need_q=True, need_k=True, need_v=True, group=None):
         """(dQ, dKt, dV) of the one-pass backward in Q's dtype, None where not needed; Q, Kt, V, O, m, s as the one-pass
-        forward took and gave them, dO contiguous in O's dtype"""
+        forward took and gave them, dO contiguous in O's dtype.  group: Kt and V (and dKt, dV) have b / group heads
+        (bsmr_sparse_attention_qkv_gqa_backward_16)"""
         b, K = self._check(Q, "Q", self.M, None)
-        self._check(Kt, "Kt", self.N, (b,))
-        _, Kv = self._check(V, "V", self.N, (b,))
+        kv = (b,) if group is None else (b // group,)
+        self._check(Kt, "Kt", self.N, kv)
+        _, Kv = self._check(V, "V", self.N, kv)
         self._check(O, "O", self.M, (b,))
         self._check(dO, "dO", self.M, (b,))
         if dO.shape != O.shape or dO.dtype != O.dtype:
@@ -824,9 +829,12 @@ class SparseOperator:
         dKt = torch.empty_like(Kt) if need_k else None
         dV = torch.empty_like(V) if need_v else None
         ptr = lambda t: 0 if t is None else t.data_ptr()
-        eng.sparse_attention_qkv_backward_16(self._bw, K, Kv, float(scale), Q.data_ptr(), Kt.data_ptr(), V.data_ptr(),
-                                             O.data_ptr(), dO.data_ptr(), m.data_ptr(), s.data_ptr(), ptr(dQ), ptr(dKt),
-                                             ptr(dV), b or 1, self._stream(), mode=_MODE16[Q.dtype])
+        args = (self._bw, K, Kv, float(scale), Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(),
+                m.data_ptr(), s.data_ptr(), ptr(dQ), ptr(dKt), ptr(dV), b or 1)
+        if group is None:
+            eng.sparse_attention_qkv_backward_16(*args, self._stream(), mode=_MODE16[Q.dtype])
+        else:
+            eng.sparse_attention_qkv_gqa_backward_16(*args, group, self._stream(), mode=_MODE16[Q.dtype])
         return dQ, dKt, dV
 
     def _attention_backward(self, v, m, s, dW, O, dO, scale):
@@ -1088,7 +1096,8 @@ class _AttentionOnePassBwd(_AttentionOnePass):
 
 class _AttentionOnePassGqa(torch.autograd.Function):
     """attention(one_pass=True) with grouped key/value heads (group = query heads per KV head): the forward is one grouped
-    call; there is no grouped backward kernel, so the backward is _AttentionOnePass's (or _AttentionOnePassBwd's) on the
+    call.  one_pass_backward=True: the backward is one grouped call as well, on the operands as they are - dKt and dV come
+    out per KV head, rounded once from the fp32 sum over the group.  Otherwise the backward is _AttentionOnePass's on the
     repeated 16-bit Kt and V, with dKt and dV summed over each group in fp32 and rounded once"""
     @staticmethod
     def forward(ctx, op: SparseOperator, Q, Kt, V, scale, group, one_pass_backward):
@@ -1105,15 +1114,15 @@ class _AttentionOnePassGqa(torch.autograd.Function):
         if not (need_q or need_k or need_v):
             return (None,) * 7
         Q, Kt, V, O, m, s = ctx.saved_tensors
-        Kr, Vr = Kt.repeat_interleave(g, 0), V.repeat_interleave(g, 0)   # b N (K + Kv) elements: nothing of size nnz
         dO = _grad(dO, O.dtype)
         if ctx.one_pass_backward:
-            dQ, dKr, dVr = op._attention_qkv_backward(Q, Kr, Vr, O, dO, m, s, ctx.scale, need_q, need_k, need_v)
-        else:
-            P = op._sddmm(Q, Kr)   # the scores exist only from here on
-            dP, W = op._attention_backward(P, m, s, op._sddmm(dO, Vr), O, dO, ctx.scale)
-            dVr = op._spmm(W, dO, True) if need_v else None
-            dQ, dKr = op._sddmm_backward(dP, Q, Kr, need_q, need_k) if need_q or need_k else (None, None)
+            dQ, dKt, dV = op._attention_qkv_backward(Q, Kt, V, O, dO, m, s, ctx.scale, need_q, need_k, need_v, group=g)
+            return None, dQ, dKt, dV, None, None, None
+        Kr, Vr = Kt.repeat_interleave(g, 0), V.repeat_interleave(g, 0)   # b N (K + Kv) elements: nothing of size nnz
+        P = op._sddmm(Q, Kr)   # the scores exist only from here on
+        dP, W = op._attention_backward(P, m, s, op._sddmm(dO, Vr), O, dO, ctx.scale)
+        dVr = op._spmm(W, dO, True) if need_v else None
+        dQ, dKr = op._sddmm_backward(dP, Q, Kr, need_q, need_k) if need_q or need_k else (None, None)
         fold = lambda d, t: None if d is None else d.view((-1, g) + d.shape[1:]).sum(1, dtype=torch.float32).to(t.dtype)
         return None, dQ, fold(dKr, Kt), fold(dVr, V), None, None, None
 

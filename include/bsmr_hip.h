@@ -950,6 +950,37 @@ int bsmr_sparse_attention_qkv_gqa_16(bsmr_backward *bw, uint32_t K, uint32_t Kv,
                                      const void *Kt16_dev, const void *V16_dev, void *O16_dev, float *m_dev, float *s_dev,
                                      uint32_t num_batches, uint32_t kv_group, int compute_mode, void *stream);
 
+/* ---- One-pass backward of sparse attention with grouped key/value heads (revision 5, added without any layout change) ----
+ * bsmr_sparse_attention_qkv_backward_16 for the grouped forward above: Q, O, dO, dQ, m and s have num_batches = b query
+ * heads; Kt, V, dKt and dV have b / g heads, g = kv_group; query head h reads KV head h / g.  Nothing is repeated in memory
+ * and nothing is folded afterwards: the gradients of a KV head are summed over its group inside the kernel.
+ * Per entry the statements are those of "One-pass backward of sparse attention" (p_t, z_t, e_t, w_t, dW_t, D_r, dz_t, the
+ * select on w_t = 0), so both sides see the bits the ungrouped call sees on Kt and V repeated g times.
+ *   dQ:  bit for bit the dQ of bsmr_sparse_attention_qkv_backward_16 on Kt and V repeated g times along the head axis -
+ *        direct and split rows.  One wave serves up to 4 heads of a group and reads each gathered row of Kt and V once.
+ *   dKt[j][c] = sum over the heads h of group j and the entries t of column c of dz_t Q[h][r_t], dV[j][c] likewise of
+ *        w_t dO[h][r_t]: each term one fmaf, each sum rounded ONCE to 16 bits.  Summation order of a column's list (of
+ *        each chunk of a list longer than BSMR_BACKWARD_CHUNK): sixteen chains from +0, chain i over the heads of the group
+ *        in ascending order and, within a head, over the entries i, i + 16, i + 32, ... in ascending row; the chains added
+ *        as a butterfly over the chain offsets 1, 2, 4, 8; chunk sums added in chunk order.  This differs from the sum of
+ *        the ungrouped call's g rounded head gradients: it is the same mathematical sum with one rounding instead of g + 1.
+ * A NaN in row r of Q or dO of head h reaches dQ[h][r] and the dKt / dV rows of KV head h / g at the columns row r stores,
+ * and nothing else; a dead row (m = -inf) of any head contributes nothing.  A row or column without entries gets +0.  One
+ * writer per element, no atomics: bitwise reproducible.  Any of dQ16_dev, dKt16_dev, dV16_dev may be NULL: that gradient is
+ * not computed.
+ * Limits: K and Kv multiples of 32 in 32 ... 256.  kv_group = 1 is bsmr_sparse_attention_qkv_backward_16 itself.
+ * Workspace, in floats: the row partials [b][row chunk slots][K], the column partials [b / g][column chunk slots][K + Kv],
+ * then D [b][M] - never more than the ungrouped call's for b batches, so bsmr_sparse_attention_qkv_backward_reserve(K, Kv,
+ * num_batches) covers it.
+ * Checked before any device call, in this order: a NULL handle or a non-finite scale, kv_group = 0 or not a divisor of
+ * num_batches (BSMR_ERR_INVALID_ARG), K or Kv (BSMR_ERR_UNSUPPORTED_K), then compute_mode, the batches and the pointers as
+ * bsmr_sparse_attention_qkv_backward_16.  num_batches = 0 is a no-op. */
+int bsmr_sparse_attention_qkv_gqa_backward_16(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                              const void *Kt16_dev, const void *V16_dev, const void *O16_dev,
+                                              const void *dO16_dev, const float *m_dev, const float *s_dev, void *dQ16_dev,
+                                              void *dKt16_dev, void *dV16_dev, uint32_t num_batches, uint32_t kv_group,
+                                              int compute_mode, void *stream);
+
 /* ---- fp8 keys and values (revision 5, added without any layout change; no reference counterpart) ----
  * The column-side operand - B / Kt of the SDDMM, X / V of the SpMM and of the fused attention - may be OCP fp8, one byte per
  * element, as an fp8 KV cache holds it: fp8_format BSMR_FP8_E4M3 (e4m3fn: no infinity, two NaN codes) or BSMR_FP8_E5M2 (two

@@ -23,7 +23,9 @@ is the blocks' entries / nnz: what the blocked kernel serves; the rest is the re
 --steps: only the 16-bit step and peak columns of the first form (fused, one-pass, one-pass with its own backward).
 --kv-group G [--features K]: instead of the above, the 16-bit forward with G query heads per key/value head, 1 and 2 KV
 heads (b = G and 2 G), K = Kv = 128 or --features: the repeat_interleave of Kt and V on its own, the fused path and the
-one-pass call on the repeated operands, and the grouped call (bsmr_sparse_attention_qkv_gqa_16) on the operands as they are.
+one-pass call on the repeated operands, and the grouped call (bsmr_sparse_attention_qkv_gqa_16) on the operands as they are;
+then the backward on the forward's (O, m, s): repeat_interleave + bsmr_sparse_attention_qkv_backward_16 on b heads + the fp32
+fold of dKt and dV (bwd_repeated) against bsmr_sparse_attention_qkv_gqa_backward_16 (bwd_grouped).
 Usage: python tools/attention_lab.py [--steps | --kv FORMAT | --blocks S | --kv-group G] [--out FILE] [shape ...]
 (one JSON line per shape)"""
 import argparse
@@ -251,7 +253,22 @@ def main_gqa(names, out, g, Kw):
                                        y.view(torch.int32 if y.dtype == torch.float32 else torch.int16))
                            for x, y in zip(op._attention_qkv_gqa(Q, Kt, V, scale, g), op._attention_qkv(Q, Kr, Vr, scale)))
                 line[f"same_bits_{key}"] = same
-                del Q, Kt, V, Kr, Vr
+                # the backward: what _AttentionOnePassGqa.backward ran before the grouped kernel (repeat, the one-pass backward
+                # on b heads, the fold) against the grouped call on the operands as they are
+                eng.sparse_attention_qkv_backward_reserve(op._bw, Kw, Kw, b)
+                O, m, s = op._attention_qkv_gqa(Q, Kt, V, scale, g)
+                H = torch.randn(b, rows, Kw, device=dev, generator=gen_).to(dtype)
+                fold = lambda d, t: d.view((-1, g) + d.shape[1:]).sum(1, dtype=torch.float32).to(t.dtype)
+
+                def repeated():
+                    dQ, dKr, dVr = op._attention_qkv_backward(Q, Kt.repeat_interleave(g, 0), V.repeat_interleave(g, 0), O, H, m, s, scale)
+                    return dQ, fold(dKr, Kt), fold(dVr, V)
+
+                grouped = lambda: op._attention_qkv_backward(Q, Kt, V, O, H, m, s, scale, group=g)
+                us[f"bwd_repeated_{key}"] = windows(repeated)
+                us[f"bwd_grouped_{key}"] = windows(grouped)
+                line[f"bwd_same_dq_bits_{key}"] = torch.equal(grouped()[0].view(torch.int16), repeated()[0].view(torch.int16))
+                del Q, Kt, V, Kr, Vr, O, m, s, H
         line["us"] = us
         text = json.dumps(line)
         print(text, flush=True)
