@@ -12,15 +12,22 @@ namespace {
 static_assert(kQkvKvE4M3 == BSMR_FP8_E4M3 && kQkvKvE5M2 == BSMR_FP8_E5M2, "an fp8_format is passed on as the KV format");
 
 // fp4: e2m1 codes (fp8Format is then unused), otherwise fp8 codes of the caller's fp8Format; mx: the call carries block
-// scales (NULL only with nnz = 0)
-int attentionQkvKvCall(bsmr_backward* bw, uint32_t K, uint32_t Kv, float scale, const void* Q16, const void* Kt, const void* Kts,
-                       const void* V, const void* Vs, void* O16, float* m, float* sOut, uint32_t nb, int mode, int fp8Format,
-                       bool fp4, bool mx, void* stream) {
+// scales (NULL only with nnz = 0).  The checks of a quantised one-pass call, grouped or not, in the documented order.
+int attentionQkvKvCheck(bsmr_backward* bw, uint32_t K, uint32_t Kv, float scale, const void* Q16, const void* Kt, const void* Kts,
+                        const void* V, const void* Vs, void* O16, float* m, float* sOut, uint32_t nb, int mode, int fp8Format,
+                        bool fp4, bool mx) {
     if (!bw || !std::isfinite(scale)) return BSMR_ERR_INVALID_ARG;
     if (!qkvDim(K) || !qkvDim(Kv)) return BSMR_ERR_UNSUPPORTED_K;
     if (fp4 ? !is16(mode) : !validFp8(mode, fp8Format)) return BSMR_ERR_INVALID_ARG;
     if (int st = checkAttentionCall(bw, Kv, scale, true, mode, nb, {Q16, Kt, V}, {}, {O16, m, sOut})) return st;
     if ((mx && bw->nnz && (!Kts || !Vs)) || !aligned16(O16) || !aligned4(m) || !aligned4(sOut)) return BSMR_ERR_INVALID_ARG;
+    return BSMR_OK;
+}
+
+int attentionQkvKvCall(bsmr_backward* bw, uint32_t K, uint32_t Kv, float scale, const void* Q16, const void* Kt, const void* Kts,
+                       const void* V, const void* Vs, void* O16, float* m, float* sOut, uint32_t nb, int mode, int fp8Format,
+                       bool fp4, bool mx, void* stream) {
+    if (int st = attentionQkvKvCheck(bw, K, Kv, scale, Q16, Kt, Kts, V, Vs, O16, m, sOut, nb, mode, fp8Format, fp4, mx)) return st;
     if (nb == 0) return BSMR_OK;
     BSMR_HIP(hipSetDevice(bw->device));
     if (int st = growWork(bw, qkvWorkFloats(bw, Kv, nb))) return st;

@@ -98,3 +98,13 @@ hipError_t bsmrLaunchAttnQkvKv(const bsmr::BwItem* items, uint32_t numItems, con
                                const uint8_t* V, const uint8_t* Vs, uint16_t* O, float* m, float* s, float* partial, float* sPart,
                                float* mPart, uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots,
                                uint32_t numBatches, bool bf16, int kvFormat, bool mx, hipStream_t stream);
+
+// The one entry of csrc/attention_qkv_gqa_kv.hip: bsmrLaunchAttnQkvKv for grouped key/value heads - attnQkvGqaKv
+// (csrc/attention_qkv_gqa_kv_kernels.hpp), ending in bsmrLaunchAttnQkvMerge.  Q, O, m, s and the partials have numBatches
+// query heads; Kt, V, Ks and Vs numBatches / kvGroup heads; query head h reads KV head h / kvGroup.  kvGroup >= 2 divides
+// numBatches, K and Kv are at most 256 (the caller checked).
+hipError_t bsmrLaunchAttnQkvGqaKv(const bsmr::BwItem* items, uint32_t numItems, const bsmr::BwSplit* splits, uint32_t numSplits,
+                                  const uint32_t* src, float scale, const uint16_t* Q, const uint8_t* Kt, const uint8_t* Ks,
+                                  const uint8_t* V, const uint8_t* Vs, uint16_t* O, float* m, float* s, float* partial,
+                                  float* sPart, float* mPart, uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots,
+                                  uint32_t numBatches, uint32_t kvGroup, bool bf16, int kvFormat, bool mx, hipStream_t stream);

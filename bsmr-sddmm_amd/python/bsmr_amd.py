@@ -266,6 +266,12 @@ HIP_SYMBOLS = {
                                          [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_qkv_kv4_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
                                          [C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_gqa_kv8": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
+                                          [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_gqa_kv8_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
+                                             [C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_gqa_kv4_mx": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 8 +
+                                             [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_qkv_backward_reserve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bsmr_sparse_attention_qkv_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 10 +
                                               [C.c_uint32, C.c_int, C.c_void_p]),
@@ -1008,6 +1014,39 @@ def sparse_attention_qkv_kv4_mx(bw, K: int, Kv: int, scale: float, Q_ptr: int, K
     _check(hip().bsmr_sparse_attention_qkv_kv4_mx(bw, K, Kv, scale, Q_ptr or None, Kt4_ptr or None, Kts_ptr or None,
                                                   V4_ptr or None, Vs_ptr or None, O_ptr or None, m_ptr or None, s_ptr or None,
                                                   num_batches, mode, stream), "bsmr_sparse_attention_qkv_kv4_mx")
+
+
+# --- the same with grouped key/value heads: Q, O, m, s have num_batches query heads, the codes and scales num_batches /
+# kv_group; query head h reads KV head h // kv_group.  The bits of the ungrouped call on repeat_interleaved codes and scales;
+# K, Kv up to 256 when kv_group > 1 (include/bsmr_hip.h "One-pass grouped-head sparse attention on fp8, MXFP8 and MXFP4 keys
+# and values") ---
+def sparse_attention_qkv_gqa_kv8(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt8_ptr: int, V8_ptr: int, O_ptr: int,
+                                 m_ptr: int, s_ptr: int, num_batches: int = 1, kv_group: int = 1, stream: int = 0,
+                                 mode=COMPUTE_F16, fmt=FP8_E4M3):
+    """sparse_attention_qkv_kv8 with grouped key/value heads: unscaled fp8 codes, fmt FP8_E4M3 / FP8_E5M2"""
+    _check(hip().bsmr_sparse_attention_qkv_gqa_kv8(bw, K, Kv, scale, Q_ptr or None, Kt8_ptr or None, V8_ptr or None,
+                                                   O_ptr or None, m_ptr or None, s_ptr or None, num_batches, kv_group, mode, fmt,
+                                                   stream), "bsmr_sparse_attention_qkv_gqa_kv8")
+
+
+def sparse_attention_qkv_gqa_kv8_mx(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt8_ptr: int, Kts_ptr: int, V8_ptr: int,
+                                    Vs_ptr: int, O_ptr: int, m_ptr: int, s_ptr: int, num_batches: int = 1, kv_group: int = 1,
+                                    stream: int = 0, mode=COMPUTE_F16, fmt=FP8_E4M3):
+    """sparse_attention_qkv_kv8_mx with grouped key/value heads: the scales [b/g][N][K/32] and [b/g][N][Kv/32] E8M0 bytes"""
+    _check(hip().bsmr_sparse_attention_qkv_gqa_kv8_mx(bw, K, Kv, scale, Q_ptr or None, Kt8_ptr or None, Kts_ptr or None,
+                                                      V8_ptr or None, Vs_ptr or None, O_ptr or None, m_ptr or None,
+                                                      s_ptr or None, num_batches, kv_group, mode, fmt, stream),
+           "bsmr_sparse_attention_qkv_gqa_kv8_mx")
+
+
+def sparse_attention_qkv_gqa_kv4_mx(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt4_ptr: int, Kts_ptr: int, V4_ptr: int,
+                                    Vs_ptr: int, O_ptr: int, m_ptr: int, s_ptr: int, num_batches: int = 1, kv_group: int = 1,
+                                    stream: int = 0, mode=COMPUTE_F16):
+    """sparse_attention_qkv_kv4_mx with grouped key/value heads: e2m1 codes, two per byte, the scales mandatory"""
+    _check(hip().bsmr_sparse_attention_qkv_gqa_kv4_mx(bw, K, Kv, scale, Q_ptr or None, Kt4_ptr or None, Kts_ptr or None,
+                                                      V4_ptr or None, Vs_ptr or None, O_ptr or None, m_ptr or None,
+                                                      s_ptr or None, num_batches, kv_group, mode, stream),
+           "bsmr_sparse_attention_qkv_gqa_kv4_mx")
 
 
 # --- one-pass backward of sparse attention: dQ, dKt, dV with scores and weights in registers only ---

@@ -336,8 +336,14 @@ class SparseOperator:
         bits of one_pass_backward=True on repeat_interleaved Kt and V, dKt and dV come out per KV head, each rounded once from
         an fp32 sum over the whole group - nothing is repeated and nothing is folded.  With the default False the backward
         repeats the 16-bit Kt and V (b N (K + Kv) elements, nothing of size nnz), runs one_pass=True's backward, sums dKt and
-        dV over each group in fp32 and rounds once."""
-        group = self._check_grouped(Q, Kt, V, blocks) if one_pass else None
+        dV over each group in fp32 and rounds once.
+        Grouped key/value heads on a quantised cache (one_pass=True, Kt and V both one fp8 dtype or both fp4, Kt_scale and
+        V_scale both given, with bk heads like the codes): one kernel reads the cache bytes in place and gathers and widens
+        each row once per group (bsmr_sparse_attention_qkv_gqa_kv8_mx / _kv4_mx) - the bits of one_pass=True on
+        repeat_interleaved codes and scales; K and Kv at most 256.  A gradient to Q alone: the backward repeats the codes and
+        scales (b N (K + Kv) bytes or fewer) and is the ungrouped quantised form's.  Unscaled grouped fp8 is refused here
+        (pass scale codes of 127) and served by engine.sparse_attention_qkv_gqa_kv8."""
+        group = self._check_grouped(Q, Kt, V, blocks, Kt_scale, V_scale) if one_pass else None
         if one_pass_backward:
             self._check_one_pass_backward(Q, Kt, V, one_pass, blocks)
         if blocks:
@@ -349,8 +355,7 @@ class SparseOperator:
             scale = Q.shape[-1] ** -0.5 if scale is None else scale
             if group is not None:
                 if quantised:
-                    raise ValueError(f"Kt: dtype {Kt.dtype} with grouped key/value heads - the grouped form takes "
-                                     "torch.float16 or torch.bfloat16 keys and values")
+                    return _AttentionOnePassGqaKv.apply(self, Q, Kt, V, scale, Kts, Vs, group)
                 return _AttentionOnePassGqa.apply(self, Q, Kt, V, scale, group, one_pass_backward)
             if quantised:
                 return _AttentionOnePassKv.apply(self, Q, Kt, V, scale, Kts, Vs)
@@ -687,7 +692,7 @@ class SparseOperator:
         return True, self._check_scale(Kt_scale, "Kt_scale", Kt), self._check_scale(V_scale, "V_scale", V)
 
     @staticmethod
-    def _check_grouped(Q, Kt, V, blocks):
+    def _check_grouped(Q, Kt, V, blocks, Kt_scale=None, V_scale=None):
         """g = b / bk when attention(one_pass=True) is called with grouped key/value heads, None when it is not; the limits
         of the grouped form, named before any device work"""
         if not all(isinstance(t, torch.Tensor) and t.dim() == 3 for t in (Q, Kt, V)):
@@ -701,13 +706,13 @@ class SparseOperator:
             raise ValueError(f"Kt, V: {bk} key/value heads do not divide the {b} heads of Q")
         if blocks:
             raise ValueError("blocks=True with grouped key/value heads: the blocked form has no grouped kernel")
-        for t, name in ((Kt, "Kt"), (V, "V")):
-            if _is8(t) or _is4(t):
-                raise ValueError(f"{name}: dtype {t.dtype} with grouped key/value heads - the grouped form takes "
-                                 "torch.float16 or torch.bfloat16 keys and values")
+        if _is8(Kt) and _is8(V) and Kt_scale is None and V_scale is None:
+            raise ValueError(f"Kt, V: dtype {Kt.dtype} without scales with grouped key/value heads - a grouped fp8 cache needs "
+                             "Kt_scale / V_scale (scale codes of 127 everywhere are unit scales); "
+                             "engine.sparse_attention_qkv_gqa_kv8 takes the unscaled form")
         for t, name in ((Q, "Q"), (Kt, "Kt"), (V, "V")):
-            if t.shape[-1] > ONE_PASS_GROUPED_MAX_K:
-                raise ValueError(f"{name}: {t.shape[-1]} features - grouped key/value heads take K and Kv in "
+            if _k_of(t) > ONE_PASS_GROUPED_MAX_K:
+                raise ValueError(f"{name}: {_k_of(t)} features - grouped key/value heads take K and Kv in "
                                  f"32 ... {ONE_PASS_GROUPED_MAX_K}")
         return b // bk
 
@@ -784,12 +789,15 @@ class SparseOperator:
                                         m.data_ptr(), s.data_ptr(), b, group, self._stream(), mode=_MODE16[Q.dtype])
         return O, m, s
 
-    def _attention_qkv_kv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, Kts=None, Vs=None):
-        """_attention_qkv on fp8 or fp4 Kt and V of one dtype; Kts / Vs: their MX block scales (uint8), both or neither"""
+    def _attention_qkv_kv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, Kts=None, Vs=None, group=None):
+        """_attention_qkv on fp8 or fp4 Kt and V of one dtype; Kts / Vs: their MX block scales (uint8), both or neither.
+        group: grouped key/value heads - Q (b, M, K), the codes and scales with b / group heads
+        (bsmr_sparse_attention_qkv_gqa_kv8 / _kv8_mx / _kv4_mx)"""
         b, K = self._check(Q, "Q", self.M, None)
         fp4 = _is4(Kt)
-        _, K2 = self._check4(Kt, "Kt", self.N, (b,)) if fp4 else self._check(Kt, "Kt", self.N, (b,), fp8=True)
-        _, Kv = self._check4(V, "V", self.N, (b,)) if fp4 else self._check(V, "V", self.N, (b,), fp8=True)
+        kv = (b,) if group is None else (b // group,)
+        _, K2 = self._check4(Kt, "Kt", self.N, kv) if fp4 else self._check(Kt, "Kt", self.N, kv, fp8=True)
+        _, Kv = self._check4(V, "V", self.N, kv) if fp4 else self._check(V, "V", self.N, kv, fp8=True)
         if K2 != K:
             raise ValueError(f"Q and Kt disagree on K ({K} vs {K2})")
         try:
@@ -801,16 +809,22 @@ class SparseOperator:
         O = torch.empty((self.M, Kv) if b is None else (b, self.M, Kv), dtype=Q.dtype, device=self.device)
         m = torch.empty((self.M,) if b is None else (b, self.M), dtype=torch.float32, device=self.device)
         s = torch.empty_like(m)
-        out = (O.data_ptr(), m.data_ptr(), s.data_ptr(), b or 1, self._stream())
-        if fp4:
-            eng.sparse_attention_qkv_kv4_mx(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), Kts.data_ptr(), V.data_ptr(),
-                                            Vs.data_ptr(), *out, mode=_MODE16[Q.dtype])
-        elif Kts is not None:
-            eng.sparse_attention_qkv_kv8_mx(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), Kts.data_ptr(), V.data_ptr(),
-                                            Vs.data_ptr(), *out, mode=_MODE16[Q.dtype], fmt=_MODE8[Kt.dtype])
+        if group is None:
+            kv4_mx, kv8_mx, kv8 = eng.sparse_attention_qkv_kv4_mx, eng.sparse_attention_qkv_kv8_mx, eng.sparse_attention_qkv_kv8
+            out = (O.data_ptr(), m.data_ptr(), s.data_ptr(), b or 1, self._stream())
         else:
-            eng.sparse_attention_qkv_kv8(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), *out,
-                                         mode=_MODE16[Q.dtype], fmt=_MODE8[Kt.dtype])
+            kv4_mx, kv8_mx = eng.sparse_attention_qkv_gqa_kv4_mx, eng.sparse_attention_qkv_gqa_kv8_mx
+            kv8 = eng.sparse_attention_qkv_gqa_kv8
+            out = (O.data_ptr(), m.data_ptr(), s.data_ptr(), b, group, self._stream())
+        if fp4:
+            kv4_mx(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), Kts.data_ptr(), V.data_ptr(), Vs.data_ptr(), *out,
+                   mode=_MODE16[Q.dtype])
+        elif Kts is not None:
+            kv8_mx(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), Kts.data_ptr(), V.data_ptr(), Vs.data_ptr(), *out,
+                   mode=_MODE16[Q.dtype], fmt=_MODE8[Kt.dtype])
+        else:
+            kv8(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), *out, mode=_MODE16[Q.dtype],
+                fmt=_MODE8[Kt.dtype])
         return O, m, s
 
     def _attention_qkv_backward(self, Q, Kt, V, O, dO, m, s, scale, need_q=True, need_k=True, need_v=True, group=None):
@@ -1149,17 +1163,44 @@ class _AttentionOnePassKv(torch.autograd.Function):
         return O
 
     @staticmethod
-    @once_differentiable
-    def backward(ctx, dO):
+    def _dq(ctx, dO, Kt, V, Kts, Vs):
+        """dQ from the saved Q, O, m, s and the codes and scales given, one KV head per query head"""
         op = ctx.op
-        if not ctx.needs_input_grad[1]:
-            return None, None, None, None, None, None, None
-        Q, Kt, V, O, m, s = ctx.saved_tensors
+        Q, _, _, O, m, s = ctx.saved_tensors
         dO = _grad(dO, O.dtype)
         sddmm, spmm = (op._sddmm_b4, op._spmm_x4) if _is4(Kt) else (op._sddmm_b8, op._spmm_x8)
-        P = sddmm(Q, Kt, ctx.Kts)   # the scores exist only from here on
-        dP, _ = op._attention_backward(P, m, s, sddmm(dO, V, ctx.Vs), O, dO, ctx.scale)
-        return None, spmm(dP, Kt, Q.dtype, ctx.Kts), None, None, None, None, None
+        P = sddmm(Q, Kt, Kts)   # the scores exist only from here on
+        dP, _ = op._attention_backward(P, m, s, sddmm(dO, V, Vs), O, dO, ctx.scale)
+        return spmm(dP, Kt, Q.dtype, Kts)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None, None
+        _, Kt, V = ctx.saved_tensors[:3]
+        return None, _AttentionOnePassKv._dq(ctx, dO, Kt, V, ctx.Kts, ctx.Vs), None, None, None, None, None
+
+
+class _AttentionOnePassGqaKv(_AttentionOnePassKv):
+    """attention(one_pass=True) on fp8 or fp4 Kt and V with grouped key/value heads (group = query heads per KV head): the
+    forward is one grouped call on the cache as it is.  The backward gives dQ alone: _AttentionOnePassKv's on the repeated
+    codes and scales (b N (K + Kv) bytes or fewer, nothing of size nnz beyond what that backward makes)"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, Q, Kt, V, scale, Kts, Vs, group):
+        O, m, s = op._attention_qkv_kv(Q, Kt, V, scale, Kts, Vs, group=group)
+        ctx.op, ctx.scale, ctx.Kts, ctx.Vs, ctx.group = op, float(scale), Kts, Vs, group
+        ctx.save_for_backward(Q, Kt, V, O, m, s)
+        return O
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dO):
+        if not ctx.needs_input_grad[1]:
+            return (None,) * 8
+        _, Kt, V = ctx.saved_tensors[:3]
+        rep = lambda t: t.view(torch.uint8).repeat_interleave(ctx.group, 0).view(t.dtype)   # (codes move as bytes)
+        return (None, _AttentionOnePassKv._dq(ctx, dO, rep(Kt), rep(V), rep(ctx.Kts), rep(ctx.Vs))) + (None,) * 6
 
 
 class _SoftmaxSpMM8(torch.autograd.Function):

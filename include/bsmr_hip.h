@@ -981,6 +981,40 @@ int bsmr_sparse_attention_qkv_gqa_backward_16(bsmr_backward *bw, uint32_t K, uin
                                               void *dKt16_dev, void *dV16_dev, uint32_t num_batches, uint32_t kv_group,
                                               int compute_mode, void *stream);
 
+/* ---- One-pass grouped-head sparse attention on fp8, MXFP8 and MXFP4 keys and values (revision 5, added without any layout
+ * change) ----
+ * bsmr_sparse_attention_qkv_kv8 / _kv8_mx / _kv4_mx for models whose query heads share key/value heads: a GQA / MQA model
+ * with a quantised KV cache.  Q [b][M][K], O [b][M][Kv], m and s [b][M] have num_batches = b query heads; the codes Kt and V
+ * and the scales Kts [b/g][N][K/32] and Vs [b/g][N][Kv/32] have b / g heads, g = kv_group, in the formats and layouts of the
+ * ungrouped calls.  Query head h reads KV head h / g.  One wave serves up to 8 heads of a group: each cache row is gathered
+ * once and widened once (and, with scales, each element of V multiplied by its scale once) for all of them; nothing is
+ * repeated or dequantised in memory.
+ * Contract: every head runs the statement sequence of "One-pass sparse attention on fp8, MXFP8 and MXFP4 keys and values" on
+ * the same values, so O, m and s are bit for bit those of the ungrouped call of the same name on codes and scales repeated g
+ * times along the head axis - empty rows, -inf rows (the skip while m = -inf is kept per head), split rows and the NaN of a
+ * NaN code or scale code 255 included.  That section's forward bound holds unchanged.
+ * Limits: K and Kv multiples of 32 in 32 ... 256 when kv_group > 1.  kv_group = 1 is the ungrouped call itself (the same
+ * kernel and bits, K and Kv up to 512).
+ * Workspace: that of bsmr_sparse_attention_qkv_16, indexed by query head; bsmr_sparse_attention_qkv_reserve(K, Kv,
+ * num_batches) sizes it.
+ * Each function has the argument list of its ungrouped namesake with kv_group directly after num_batches.  Checked before
+ * any device work, in this order: everything the ungrouped call checks, in its order; kv_group = 0 or not a divisor of
+ * num_batches (BSMR_ERR_INVALID_ARG); kv_group > 1 with K or Kv above 256 (BSMR_ERR_UNSUPPORTED_K).  num_batches = 0 is a
+ * no-op behind them.  With nnz = 0 the inputs may be NULL. */
+int bsmr_sparse_attention_qkv_gqa_kv8(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                      const void *Kt8_dev, const void *V8_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                      uint32_t num_batches, uint32_t kv_group, int compute_mode, int fp8_format,
+                                      void *stream);
+int bsmr_sparse_attention_qkv_gqa_kv8_mx(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                         const void *Kt8_dev, const void *Kt_scales_dev, const void *V8_dev,
+                                         const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                         uint32_t num_batches, uint32_t kv_group, int compute_mode, int fp8_format,
+                                         void *stream);
+int bsmr_sparse_attention_qkv_gqa_kv4_mx(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                         const void *Kt4_dev, const void *Kt_scales_dev, const void *V4_dev,
+                                         const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev,
+                                         uint32_t num_batches, uint32_t kv_group, int compute_mode, void *stream);
+
 /* ---- fp8 keys and values (revision 5, added without any layout change; no reference counterpart) ----
  * The column-side operand - B / Kt of the SDDMM, X / V of the SpMM and of the fused attention - may be OCP fp8, one byte per
  * element, as an fp8 KV cache holds it: fp8_format BSMR_FP8_E4M3 (e4m3fn: no infinity, two NaN codes) or BSMR_FP8_E5M2 (two

@@ -26,7 +26,11 @@ heads (b = G and 2 G), K = Kv = 128 or --features: the repeat_interleave of Kt a
 one-pass call on the repeated operands, and the grouped call (bsmr_sparse_attention_qkv_gqa_16) on the operands as they are;
 then the backward on the forward's (O, m, s): repeat_interleave + bsmr_sparse_attention_qkv_backward_16 on b heads + the fp32
 fold of dKt and dV (bwd_repeated) against bsmr_sparse_attention_qkv_gqa_backward_16 (bwd_grouped).
-Usage: python tools/attention_lab.py [--steps | --kv FORMAT | --blocks S | --kv-group G] [--out FILE] [shape ...]
+--kv-group G --kv FORMAT: the forward on a quantised KV cache with G query heads per key/value head, 1 and 2 KV heads, K = Kv
+= 128: the repeat_interleave of codes and scales on its own, the ungrouped quantised one-pass call on the repeated codes and
+scales, and the grouped call (bsmr_sparse_attention_qkv_gqa_kv8 / _kv8_mx / _kv4_mx) on the cache as it is; same_bits compares
+the two.
+Usage: python tools/attention_lab.py [--steps | --kv FORMAT | --blocks S | --kv-group G [--kv FORMAT]] [--out FILE] [shape ...]
 (one JSON line per shape)"""
 import argparse
 import json
@@ -279,6 +283,49 @@ def main_gqa(names, out, g, Kw):
         torch.cuda.empty_cache()
 
 
+def main_gqa_kv(names, out, g, kv):
+    fmt = getattr(torch, "float4_e2m1fn_x2", None) if kv == "mxfp4" else torch.float8_e4m3fn
+    Kw = 128
+    scale = Kw ** -0.5
+    rep = lambda t: None if t is None else t.view(torch.uint8).repeat_interleave(g, 0).view(t.dtype)
+    raw = lambda x: x.view(torch.int32 if x.dtype == torch.float32 else torch.int16)
+    for name in names:
+        gen, kwargs, _ = SHAPES[name]
+        rows, cols, ro, ci = getattr(synth, gen)(**kwargs)
+        ro = np.ascontiguousarray(ro, dtype=np.uint32)
+        ci = np.ascontiguousarray(ci, dtype=np.uint32)
+        op = bsmr_torch.SparseOperator(eng.CSR.from_arrays(rows, cols, ro, ci), device=0)
+        line = {"shape": name, "kv": kv, "M": rows, "N": cols, "nnz": int(ci.size), "K": Kw, "kv_group": g}
+        us = {}
+        for bk in (1, 2):
+            b = bk * g
+            eng.sparse_attention_qkv_reserve(op._bw, Kw, Kw, b)
+            gen_ = torch.Generator(device=dev).manual_seed(7)
+            rand = lambda h, n: torch.randn(h, n, Kw, device=dev, generator=gen_)
+            quant = lambda: bsmr_torch.mx_quantize(rand(bk, cols), fmt) if kv != "fp8" else (rand(bk, cols).to(fmt), None)
+            (Kt, Kts), (V, Vs) = quant(), quant()
+            for dtype, tag in ((torch.float16, "f16"), (torch.bfloat16, "bf16")):
+                Q = rand(b, rows).to(dtype)
+                key = f"kv{bk}_{tag}"
+                us[f"repeat_{key}"] = windows(lambda: [rep(t) for t in (Kt, Kts, V, Vs)])
+                Kr, Ksr, Vr, Vsr = (rep(t) for t in (Kt, Kts, V, Vs))
+                repeated = lambda: op._attention_qkv_kv(Q, Kr, Vr, scale, Ksr, Vsr)
+                grouped = lambda: op._attention_qkv_kv(Q, Kt, V, scale, Kts, Vs, group=g)
+                us[f"fwd_one_pass_{key}"] = windows(repeated)
+                us[f"fwd_grouped_{key}"] = windows(grouped)
+                line[f"same_bits_{key}"] = all(torch.equal(raw(x), raw(y)) for x, y in zip(grouped(), repeated()))
+                del Q, Kr, Ksr, Vr, Vsr
+            del Kt, Kts, V, Vs
+        line["us"] = us
+        text = json.dumps(line)
+        print(text, flush=True)
+        if out:
+            with open(out, "a") as f:
+                f.write(text + "\n")
+        del op
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--kv-group", type=int, default=None, metavar="G",
@@ -296,9 +343,12 @@ if __name__ == "__main__":
     if unknown:
         ap.error(f"unknown shape(s) {unknown}")
     if args.kv_group is not None:
-        if args.kv or args.blocks is not None or args.kv_group < 2 or args.features % 32 or not 32 <= args.features <= 256:
-            ap.error("--kv-group takes G >= 2, K = Kv a multiple of 32 up to 256, and excludes --kv and --blocks")
-        main_gqa(args.shapes or list(SHAPES), args.out, args.kv_group, args.features)
+        if args.blocks is not None or args.kv_group < 2 or args.features % 32 or not 32 <= args.features <= 256:
+            ap.error("--kv-group takes G >= 2, K = Kv a multiple of 32 up to 256, and excludes --blocks")
+        if args.kv:
+            main_gqa_kv(args.shapes or list(SHAPES), args.out, args.kv_group, args.kv)
+        else:
+            main_gqa(args.shapes or list(SHAPES), args.out, args.kv_group, args.features)
     elif args.blocks is not None:
         if args.kv or args.blocks < 1:
             ap.error("--blocks takes S >= 1 and excludes --kv")
