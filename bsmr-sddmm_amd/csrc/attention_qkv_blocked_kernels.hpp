@@ -52,17 +52,6 @@
 
 namespace bsmr {
 
-template <int MODE>
-__device__ __forceinline__ f32x4 blkScoreStep(const u32x4 a, const u32x4 b, const f32x4 c) {
-    if constexpr (MODE == 0) {
-        typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    } else {
-        typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-}
-
 template <int MODE, int NL, int G>
 __global__ void __launch_bounds__(256)
 attnQkvBlocks(const void* __restrict__ units, uint32_t numUnits, uint32_t segments, uint32_t numSlabs,
@@ -119,7 +108,7 @@ attnQkvBlocks(const void* __restrict__ units, uint32_t numUnits, uint32_t segmen
             u32x4 qi;
             if constexpr (QLDS) qi = qMine[(4u * i + kq) ^ n];
             else qi = q[i];
-            const f32x4 next = blkScoreStep<MODE>(kt[i], qi, p);
+            const f32x4 next = mfmaLowp<MODE>(kt[i], qi, p);
             p = (uint32_t)i < kc ? next : p;   // (wave-uniform select: exactly K / 32 steps)
         }
 #pragma unroll

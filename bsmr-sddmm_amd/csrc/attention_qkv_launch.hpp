@@ -31,6 +31,15 @@ hipError_t bsmrLaunchAttnQkvGqa(const bsmr::BwItem* items, uint32_t numItems, co
                                 uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots, uint32_t numBatches, uint32_t kvGroup,
                                 bool bf16, hipStream_t stream);
 
+// The one entry of csrc/attention_qkv_gqa_mfma.hip: bsmrLaunchAttnQkvGqa's arguments on attnQkvGqaMfma
+// (csrc/attention_qkv_gqa_mfma_kernels.hpp: both products on the MFMA, up to 16 heads of a group per wave), ending in
+// bsmrLaunchAttnQkvMerge.  kvGroup >= 1 divides numBatches, K and Kv are at most 256 (the caller checked).
+hipError_t bsmrLaunchAttnQkvGqaMfma(const bsmr::BwItem* items, uint32_t numItems, const bsmr::BwSplit* splits,
+                                    uint32_t numSplits, const uint32_t* src, float scale, const uint16_t* Q, const uint16_t* Kt,
+                                    const uint16_t* V, uint16_t* O, float* m, float* s, float* partial, float* sPart,
+                                    float* mPart, uint32_t K, uint32_t Kv, uint32_t M, uint32_t N, uint32_t numSlots,
+                                    uint32_t numBatches, uint32_t kvGroup, bool bf16, hipStream_t stream);
+
 // The one entry of csrc/attention_qkv_bwd.hip: attnQkvBwdQ over the row direction's lists when dQ is asked for, attnQkvBwdKV
 // over the column direction's when dKt or dV is, each followed by attnQkvBwdReduce for its split destinations
 // (csrc/attention_qkv_bwd_kernels.hpp).  A gradient that is NULL is not computed.  D [b][M]: dO_r . O_r, already written on

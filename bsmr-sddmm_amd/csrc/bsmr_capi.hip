@@ -3677,3 +3677,4 @@ int clusterRows(int device, uint32_t rows, uint32_t cols, const uint32_t* row_of
 #include "attention_qkv_gqa_capi.hpp"
 #include "attention_qkv_gqa_bwd_capi.hpp"
 #include "attention_qkv_gqa_kv_capi.hpp"
+#include "attention_qkv_gqa_mfma_capi.hpp"

@@ -41,6 +41,16 @@ __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float acc) {
     }
 }
 
+// One step of a 16 x 16 product over 32 k on v_mfma_f32_16x16x32_f16 / _bf16: lane l holds A[l & 15][8 (l >> 4) ... + 7] in
+// a, B[8 (l >> 4) ... + 7][l & 15] in b and C[4 (l >> 4) + i][l & 15] in c[i].  The one-pass attention units on the MFMA.
+template <int MODE>
+__device__ __forceinline__ f32x4 mfmaLowp(const u32x4 a, const u32x4 b, const f32x4 c) {
+    if constexpr (MODE == 0)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
 // The element policy of the fp16 / bf16 operand copies (csrc/sddmm_kernels.hpp, "Sparse residue"): 8 elements per
 // 16-byte chunk through v_dot2c_f32_{f16,bf16} (products exact, fp32 accumulation), four steps in ascending k.
 template <int MODE>

@@ -277,6 +277,8 @@ HIP_SYMBOLS = {
                                               [C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_qkv_gqa_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
                                          [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "bsmr_sparse_attention_qkv_gqa_mfma_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 6 +
+                                              [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_sparse_attention_qkv_gqa_backward_16": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float] + [C.c_void_p] * 10 +
                                                   [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "bsmr_widen_fp8": (C.c_int,[C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
@@ -971,6 +973,17 @@ def sparse_attention_qkv_gqa_16(bw, K: int, Kv: int, scale: float, Q_ptr: int, K
     _check(hip().bsmr_sparse_attention_qkv_gqa_16(bw, K, Kv, scale, Q_ptr or None, Kt_ptr or None, V_ptr or None, O_ptr or None,
                                                   m_ptr or None, s_ptr or None, num_batches, kv_group, mode, stream),
            "bsmr_sparse_attention_qkv_gqa_16")
+
+
+def sparse_attention_qkv_gqa_mfma_16(bw, K: int, Kv: int, scale: float, Q_ptr: int, Kt_ptr: int, V_ptr: int, O_ptr: int,
+                                     m_ptr: int, s_ptr: int, num_batches: int = 1, kv_group: int = 1, stream: int = 0,
+                                     mode=COMPUTE_F16):
+    """sparse_attention_qkv_gqa_16's arguments with both products on the MFMA, up to 16 heads of a group per wave: the same
+    function in another summation order, the weights of the value product rounded to mode's format - not the bits of
+    sparse_attention_qkv_gqa_16.  Every kv_group >= 1 takes this kernel; K, Kv up to 256"""
+    _check(hip().bsmr_sparse_attention_qkv_gqa_mfma_16(bw, K, Kv, scale, Q_ptr or None, Kt_ptr or None, V_ptr or None,
+                                                       O_ptr or None, m_ptr or None, s_ptr or None, num_batches, kv_group, mode,
+                                                       stream), "bsmr_sparse_attention_qkv_gqa_mfma_16")
 
 
 # --- one-pass sparse attention over the RPHM's dense blocks: both products of the block part on the MFMA ---

@@ -309,7 +309,7 @@ class SparseOperator:
 
     def attention(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale=None, fused: bool = False,
                   out_dtype=None, Kt_scale=None, V_scale=None, one_pass: bool = False, blocks: bool = False,
-                  one_pass_backward: bool = False) -> torch.Tensor:
+                  one_pass_backward: bool = False, mfma: bool = False) -> torch.Tensor:
         """spmm(softmax(sddmm(Q, Kt), scale), V): Q (M, K), Kt (N, K), V (N, Kv), or all with a leading b; K and Kv
         positive multiples of 32; scale defaults to K**-0.5.  A row of S without entries gives a zero row.
         fused=True: softmax_spmm(sddmm(Q, Kt), V, scale) - the same function in another summation order.
@@ -342,7 +342,15 @@ class SparseOperator:
         each row once per group (bsmr_sparse_attention_qkv_gqa_kv8_mx / _kv4_mx) - the bits of one_pass=True on
         repeat_interleaved codes and scales; K and Kv at most 256.  A gradient to Q alone: the backward repeats the codes and
         scales (b N (K + Kv) bytes or fewer) and is the ungrouped quantised form's.  Unscaled grouped fp8 is refused here
-        (pass scale codes of 127) and served by engine.sparse_attention_qkv_gqa_kv8."""
+        (pass scale codes of 127) and served by engine.sparse_attention_qkv_gqa_kv8.
+        mfma=True (with one_pass=True and grouped 16-bit Kt and V, blocks=False, K and Kv at most 256): the grouped forward
+        runs both products on the MFMA with up to 16 heads of a group per wave (bsmr_sparse_attention_qkv_gqa_mfma_16).  The
+        same function in another summation order with the weights of the value product rounded to 16 bits - not the bits
+        of mfma=False; a non-finite V[c, k] at a stored entry makes feature k NaN in every live head of the wave's 16.  The
+        backward is the grouped form's on the saved (O, m, s), with and without one_pass_backward=True.  Nothing selects
+        it: the default False keeps every path and bit."""
+        if mfma:
+            self._check_mfma(Q, Kt, V, one_pass, blocks, Kt_scale, V_scale)
         group = self._check_grouped(Q, Kt, V, blocks, Kt_scale, V_scale) if one_pass else None
         if one_pass_backward:
             self._check_one_pass_backward(Q, Kt, V, one_pass, blocks)
@@ -356,7 +364,8 @@ class SparseOperator:
             if group is not None:
                 if quantised:
                     return _AttentionOnePassGqaKv.apply(self, Q, Kt, V, scale, Kts, Vs, group)
-                return _AttentionOnePassGqa.apply(self, Q, Kt, V, scale, group, one_pass_backward)
+                form = _AttentionOnePassGqaMfma if mfma else _AttentionOnePassGqa
+                return form.apply(self, Q, Kt, V, scale, group, one_pass_backward)
             if quantised:
                 return _AttentionOnePassKv.apply(self, Q, Kt, V, scale, Kts, Vs)
             if blocks:
@@ -716,6 +725,25 @@ class SparseOperator:
                                  f"32 ... {ONE_PASS_GROUPED_MAX_K}")
         return b // bk
 
+    @staticmethod
+    def _check_mfma(Q, Kt, V, one_pass, blocks, Kt_scale, V_scale):
+        """the limits of attention(mfma=True), named before any device work and before the grouped form's own"""
+        if not one_pass:
+            raise ValueError("mfma=True needs one_pass=True: it is a form of the grouped one-pass forward")
+        if blocks:
+            raise ValueError("mfma=True with blocks=True: they are two different MFMA forms, choose one")
+        tensors = all(isinstance(t, torch.Tensor) for t in (Q, Kt, V))
+        if tensors and (any(_is8(t) or _is4(t) for t in (Kt, V)) or Kt_scale is not None or V_scale is not None):
+            raise ValueError("mfma=True takes torch.float16 or torch.bfloat16 keys and values without scales; a quantised "
+                             "cache goes through mfma=False")
+        if not tensors or not all(t.dim() == 3 for t in (Q, Kt, V)) or not (
+                0 < Kt.shape[0] < Q.shape[0] and Q.shape[0] % Kt.shape[0] == 0 and V.shape[0] == Kt.shape[0]):
+            raise ValueError("mfma=True needs grouped key/value heads: Q (b, M, K), Kt (bk, N, K) and V (bk, N, Kv) with "
+                             "bk < b and b % bk == 0; ungrouped operands go through mfma=False")
+        for t, name in ((Q, "Q"), (Kt, "Kt"), (V, "V")):
+            if _k_of(t) > ONE_PASS_GROUPED_MAX_K:
+                raise ValueError(f"{name}: {_k_of(t)} features - mfma=True takes K and Kv in 32 ... {ONE_PASS_GROUPED_MAX_K}")
+
     def _check_one_pass_backward(self, Q, Kt, V, one_pass, blocks):
         """the limits attention(one_pass_backward=True) adds to one_pass=True's, named before any device work"""
         if not one_pass:
@@ -769,8 +797,9 @@ class SparseOperator:
              self._stream(), mode=_MODE16[Q.dtype])
         return O, m, s
 
-    def _attention_qkv_gqa(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, group: int):
-        """_attention_qkv with grouped key/value heads: Q (b, M, K), Kt (b / group, N, K), V (b / group, N, Kv)"""
+    def _attention_qkv_gqa(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, group: int, mfma: bool = False):
+        """_attention_qkv with grouped key/value heads: Q (b, M, K), Kt (b / group, N, K), V (b / group, N, Kv).
+        mfma: through bsmr_sparse_attention_qkv_gqa_mfma_16"""
         b, K = self._check(Q, "Q", self.M, None)
         _, K2 = self._check(Kt, "Kt", self.N, (b // group,))
         _, Kv = self._check(V, "V", self.N, (b // group,))
@@ -785,8 +814,9 @@ class SparseOperator:
         O = torch.empty((b, self.M, Kv), dtype=Q.dtype, device=self.device)
         m = torch.empty((b, self.M), dtype=torch.float32, device=self.device)
         s = torch.empty_like(m)
-        eng.sparse_attention_qkv_gqa_16(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(),
-                                        m.data_ptr(), s.data_ptr(), b, group, self._stream(), mode=_MODE16[Q.dtype])
+        call = eng.sparse_attention_qkv_gqa_mfma_16 if mfma else eng.sparse_attention_qkv_gqa_16
+        call(self._bw, K, Kv, scale, Q.data_ptr(), Kt.data_ptr(), V.data_ptr(), O.data_ptr(), m.data_ptr(), s.data_ptr(), b,
+             group, self._stream(), mode=_MODE16[Q.dtype])
         return O, m, s
 
     def _attention_qkv_kv(self, Q: torch.Tensor, Kt: torch.Tensor, V: torch.Tensor, scale, Kts=None, Vs=None, group=None):
@@ -1139,6 +1169,17 @@ class _AttentionOnePassGqa(torch.autograd.Function):
         dQ, dKr = op._sddmm_backward(dP, Q, Kr, need_q, need_k) if need_q or need_k else (None, None)
         fold = lambda d, t: None if d is None else d.view((-1, g) + d.shape[1:]).sum(1, dtype=torch.float32).to(t.dtype)
         return None, dQ, fold(dKr, Kt), fold(dVr, V), None, None, None
+
+
+class _AttentionOnePassGqaMfma(_AttentionOnePassGqa):
+    """attention(one_pass=True, mfma=True): the grouped forward on the MFMA; _AttentionOnePassGqa's backward on the saved
+    O, m, s"""
+    @staticmethod
+    def forward(ctx, op: SparseOperator, Q, Kt, V, scale, group, one_pass_backward):
+        O, m, s = op._attention_qkv_gqa(Q, Kt, V, scale, group, mfma=True)
+        ctx.op, ctx.scale, ctx.group, ctx.one_pass_backward = op, float(scale), group, one_pass_backward
+        ctx.save_for_backward(Q, Kt, V, O, m, s)
+        return O
 
 
 class _AttentionOnePassBlocks(_AttentionOnePass):

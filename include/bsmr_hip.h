@@ -1015,6 +1015,47 @@ int bsmr_sparse_attention_qkv_gqa_kv4_mx(bsmr_backward *bw, uint32_t K, uint32_t
                                          const void *V_scales_dev, void *O16_dev, float *m_dev, float *s_dev,
                                          uint32_t num_batches, uint32_t kv_group, int compute_mode, void *stream);
 
+/* ---- One-pass grouped-head sparse attention on the MFMA (revision 5, added without any layout change) ----
+ * bsmr_sparse_attention_qkv_gqa_16's arguments and function with both products on the matrix units: the heads of a KV group
+ * walk the same entries of a row, so per tile of 32 entries one wave computes S^T = Kt_tile Q_group^T and O_group^T =
+ * V_tile^T P on v_mfma_f32_16x16x32_f16 / _bf16 with up to 16 consecutive heads of the group as N.  An opt-in call with a
+ * contract of its own; no rule of the library selects it.
+ * What differs from "One-pass sparse attention with grouped key/value heads":
+ *   - O, m and s are NOT bit for bit those of the ungrouped call: the score of an entry is a chain of K / 32 MFMA steps, the
+ *     maximum and the sum of a tile of 32 entries are taken per lane over 8 scores and then over the lanes ^ 16 and ^ 32, and
+ *     the value product takes the weights e = expf(fl(z - m')) ROUNDED to the operands' 16-bit format (round to nearest
+ *     even; the flash-attention convention).  s sums the unrounded fp32 e, so (m, s) mean what they mean there and serve the
+ *     same backward calls.
+ *   - It is deterministic: no atomics, one writer per element, the same bits call to call and stream to stream.  A column
+ *     of either MFMA depends on its own head alone, so with finite V each head is bit for bit what a call on that head and
+ *     its KV head alone (num_batches = kv_group = 1) gives.
+ *   - Exact cases: a row with one finite entry returns its row of V, m = z, s = 1; equal scores give s = n and
+ *     round16(fl(sum V) / n) - the bits of bsmr_sparse_attention_qkv_gqa_16 - when the sums of V are exact in fp32 (e = 1 is
+ *     exact in 16 bits); an empty row or a row whose scores are all -inf gives +0, m = -inf, s = 0.
+ *   - A NaN in Q[h][r] reaches row r of head h alone.  A NaN in a row c of Kt reaches every head of the KV group in the rows
+ *     that store column c, and no other row: an entry past a row's end is -inf by select.
+ *   - Non-finite V (a departure from the gather): the value product of a tile is skipped only while EVERY head of the wave
+ *     is still at m = -inf; in a tile that is taken a weight of 0 still enters the product.  A non-finite V[c][k] at a stored
+ *     entry of row r therefore makes O[h][r][k] NaN for every head h of the sub-group of 16 that ends the row with m > -inf
+ *     or NaN - what a dense softmax @ V gives.  A head that ends the row at m = -inf stores +0.  Row 0 of V and of Kt never
+ *     reach a row that does not store column 0.
+ * Forward bound against fp64 on the same 16-bit inputs, with the symbols of "One-pass sparse attention" (u = 2^-24, u16 =
+ * 2^-11 / 2^-8, d, Z_r, T = min(ceil(n / 16), 32), w64) under the supposition that one 16x16x32 MFMA step errs by no more than
+ * 32 sequential fp32 roundings of its exact products:
+ *   |O_k - O64_k| <= [(exp(2d) - 1) + exp(2d) ((2n + 31 + 6T + 2 Z_r + 13) u + u16)] sum_t w64_t |V[c_t][k]|
+ *                    + (n + 2T + 2) 2^-126 max_t |V| + (fp16 only) n 2^-25 max_t |V|,   then the rounding of O:
+ *   u16 |O_k| (+ 2^-25 in fp16);   m and s keep that section's bounds.
+ * Limits: K and Kv multiples of 32 in 32 ... 256 for every kv_group >= 1 (there is no hand-off to another kernel at kv_group
+ * = 1).  Workspace: that of bsmr_sparse_attention_qkv_16, indexed by query head; bsmr_sparse_attention_qkv_reserve(K, Kv,
+ * num_batches) sizes it.
+ * Checked before any device call, in the order of bsmr_sparse_attention_qkv_gqa_16: a NULL handle or a non-finite scale,
+ * kv_group = 0 or not a divisor of num_batches (BSMR_ERR_INVALID_ARG), K or Kv (BSMR_ERR_UNSUPPORTED_K), then compute_mode,
+ * the batches and the pointers.  num_batches = 0 is a no-op.  With nnz = 0 the inputs may be NULL. */
+int bsmr_sparse_attention_qkv_gqa_mfma_16(bsmr_backward *bw, uint32_t K, uint32_t Kv, float scale, const void *Q16_dev,
+                                          const void *Kt16_dev, const void *V16_dev, void *O16_dev, float *m_dev,
+                                          float *s_dev, uint32_t num_batches, uint32_t kv_group, int compute_mode,
+                                          void *stream);
+
 /* ---- fp8 keys and values (revision 5, added without any layout change; no reference counterpart) ----
  * The column-side operand - B / Kt of the SDDMM, X / V of the SpMM and of the fused attention - may be OCP fp8, one byte per
  * element, as an fp8 KV cache holds it: fp8_format BSMR_FP8_E4M3 (e4m3fn: no infinity, two NaN codes) or BSMR_FP8_E5M2 (two

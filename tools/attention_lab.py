@@ -23,7 +23,9 @@ is the blocks' entries / nnz: what the blocked kernel serves; the rest is the re
 --steps: only the 16-bit step and peak columns of the first form (fused, one-pass, one-pass with its own backward).
 --kv-group G [--features K]: instead of the above, the 16-bit forward with G query heads per key/value head, 1 and 2 KV
 heads (b = G and 2 G), K = Kv = 128 or --features: the repeat_interleave of Kt and V on its own, the fused path and the
-one-pass call on the repeated operands, and the grouped call (bsmr_sparse_attention_qkv_gqa_16) on the operands as they are;
+one-pass call on the repeated operands, and the grouped call (bsmr_sparse_attention_qkv_gqa_16) on the operands as they are
+with its MFMA form (bsmr_sparse_attention_qkv_gqa_mfma_16, fwd_grouped_mfma; agree_mfma is max |O_mfma - O_grouped| / max |O|;
+--mfma-only times just these two, the grouped call before and after the MFMA form);
 then the backward on the forward's (O, m, s): repeat_interleave + bsmr_sparse_attention_qkv_backward_16 on b heads + the fp32
 fold of dKt and dV (bwd_repeated) against bsmr_sparse_attention_qkv_gqa_backward_16 (bwd_grouped).
 --kv-group G --kv FORMAT: the forward on a quantised KV cache with G query heads per key/value head, 1 and 2 KV heads, K = Kv
@@ -230,7 +232,7 @@ def main_blocks(names, out, S):
         torch.cuda.empty_cache()
 
 
-def main_gqa(names, out, g, Kw):
+def main_gqa(names, out, g, Kw, mfma_only=False):
     for name in names:
         gen, kwargs, _ = SHAPES[name]
         rows, cols, ro, ci = getattr(synth, gen)(**kwargs)
@@ -248,15 +250,27 @@ def main_gqa(names, out, g, Kw):
                 gen_ = torch.Generator(device=dev).manual_seed(7)
                 Q, Kt, V = (torch.randn(h, n, Kw, device=dev, generator=gen_).to(dtype) for h, n in ((b, rows), (bk, cols), (bk, cols)))
                 key = f"kv{bk}_{tag}"
+                if mfma_only:   # the two grouped forwards alone, alternating: grouped, MFMA, grouped again
+                    us[f"fwd_grouped_{key}"] = windows(lambda: op._attention_qkv_gqa(Q, Kt, V, scale, g))
+                    us[f"fwd_grouped_mfma_{key}"] = windows(lambda: op._attention_qkv_gqa(Q, Kt, V, scale, g, mfma=True))
+                    us[f"fwd_grouped_again_{key}"] = windows(lambda: op._attention_qkv_gqa(Q, Kt, V, scale, g))
+                    Og, Om = (op._attention_qkv_gqa(Q, Kt, V, scale, g, mfma=f)[0].float() for f in (False, True))
+                    line[f"agree_mfma_{key}"] = float((Om - Og).abs().max() / Og.abs().max())
+                    del Q, Kt, V, Og, Om
+                    continue
                 us[f"repeat_{key}"] = windows(lambda: (Kt.repeat_interleave(g, 0), V.repeat_interleave(g, 0)))
                 Kr, Vr = Kt.repeat_interleave(g, 0), V.repeat_interleave(g, 0)
                 us[f"fwd_fused_{key}"] = windows(lambda: op._attention(op._sddmm(Q, Kr), Vr, scale))
                 us[f"fwd_one_pass_{key}"] = windows(lambda: op._attention_qkv(Q, Kr, Vr, scale))
                 us[f"fwd_grouped_{key}"] = windows(lambda: op._attention_qkv_gqa(Q, Kt, V, scale, g))
+                us[f"fwd_grouped_mfma_{key}"] = windows(lambda: op._attention_qkv_gqa(Q, Kt, V, scale, g, mfma=True))
                 same = all(torch.equal(x.view(torch.int32 if x.dtype == torch.float32 else torch.int16),
                                        y.view(torch.int32 if y.dtype == torch.float32 else torch.int16))
                            for x, y in zip(op._attention_qkv_gqa(Q, Kt, V, scale, g), op._attention_qkv(Q, Kr, Vr, scale)))
                 line[f"same_bits_{key}"] = same
+                Og, Om = (op._attention_qkv_gqa(Q, Kt, V, scale, g, mfma=f)[0].float() for f in (False, True))
+                line[f"agree_mfma_{key}"] = float((Om - Og).abs().max() / Og.abs().max())
+                del Og, Om
                 # the backward: what _AttentionOnePassGqa.backward ran before the grouped kernel (repeat, the one-pass backward
                 # on b heads, the fold) against the grouped call on the operands as they are
                 eng.sparse_attention_qkv_backward_reserve(op._bw, Kw, Kw, b)
@@ -330,6 +344,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--kv-group", type=int, default=None, metavar="G",
                     help="time the grouped one-pass forward (G query heads per KV head) beside one-pass and fused on repeated Kt / V")
+    ap.add_argument("--mfma-only", action="store_true", help="with --kv-group: only the grouped call and its MFMA form")
     ap.add_argument("--features", type=int, default=128, metavar="K", help="K = Kv of --kv-group (default 128)")
     ap.add_argument("--kv", choices=("fp8", "mxfp8", "mxfp4"), default=None,
                     help="time the forward on a quantised KV cache: fused path against one-pass")
@@ -348,7 +363,7 @@ if __name__ == "__main__":
         if args.kv:
             main_gqa_kv(args.shapes or list(SHAPES), args.out, args.kv_group, args.kv)
         else:
-            main_gqa(args.shapes or list(SHAPES), args.out, args.kv_group, args.features)
+            main_gqa(args.shapes or list(SHAPES), args.out, args.kv_group, args.features, args.mfma_only)
     elif args.blocks is not None:
         if args.kv or args.blocks < 1:
             ap.error("--blocks takes S >= 1 and excludes --kv")
